@@ -12,19 +12,29 @@ rank*65536 + i) and the gradient is all-reduced (RCCL over xGMI, the
 torch.distributed "nccl" backend) once per minibatch, enqueued on the context's
 stream (the host never waits per minibatch); weak scaling.
 
-Prints ONE JSON line (rank 0):
+A plain run sets up, warms up, times the --steps updates, writes the last
+update's outputs if --dump-outputs is given, and prints ONE JSON line (rank 0):
+  value, ms_per_step   env-steps/s and milliseconds per timed update;
   roofline      the dominant kernel (fused minibatch forward/loss/backward):
-                algorithmic FLOP rate against the FP32 dense peak, timed with HIP
-                events on the context's stream; `traffic` = HBM bytes per launch
-                from the rocprofv3 PMC passes in pmc_traffic.json, reported only
-                when that profile was taken of the current kernel source;
-  gae_roofline  the GAE scan's algorithmic HBM rate (north star: >= 40 %);
+                algorithmic FLOP rate against the FP32 dense peak, from the HIP
+                events the timed updates record on the context's stream (no run
+                of its own); `traffic` = HBM bytes per launch from the rocprofv3
+                PMC passes in pmc_traffic.json, reported only when that profile
+                was taken of the current kernel source.
+`--full` adds what takes runs of its own (null in a plain run's line):
+  gae_roofline  the GAE scan's algorithmic HBM rate (north star: >= 40 %), from
+                isolated launches after the timed region;
   steps_to_475  global_step at which the 100-episode rolling mean return
                 (main.rs:842-853) first reaches 475 (CartPole-v1 solved, max 500),
                 for CfgB and for configs/cartpole.toml (N=32, T=128), trained
                 outside the timed region (rank 0, N=1 only);
   cpu_baseline  the CPU oracle (C restatement of the reference's ndarray path)
                 timed on a bounded sample of the same workload on this host.
+`--dump-outputs DIR` writes what a caller of the timed path holds after its last
+update as DIR/<name>.npy (dump_outputs() below): the parameters, the update's
+metrics, the normalizer states and a fixed seeded sample of the rollout buffer.
+The inputs (env seeds, initial weights, RNG stream) depend only on the
+arguments, so two builds can be compared output for output.
 `--selftest` runs the launcher, rank plumbing, barrier and max-over-ranks
 timing with gloo and no GPU work (the CPU test of the N>1 harness).
 """
@@ -58,11 +68,16 @@ def parse():
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--num-envs", type=int, default=65536, help="envs per GPU")
     p.add_argument("--num-steps", type=int, default=128)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline does not need: the isolated GAE launches (gae_roofline), "
+                        "the steps-to-475 learning runs and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
     p.add_argument("--cpu-envs", type=int, default=8192, help="CPU baseline sample size (envs)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-learning", action="store_true", help="skip the steps-to-475 runs")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-learning", action="store_true", help="with --full: skip the steps-to-475 runs")
     p.add_argument("--no-gae-isolated", action="store_true",
-                   help="skip the isolated GAE launches (kernel traces of the in-loop launches only)")
+                   help="with --full: skip the isolated GAE launches (kernel traces of the in-loop launches only)")
     p.add_argument("--selftest", action="store_true", help="N>1 harness check with gloo and no GPU work")
     p.add_argument("--host-cpus", type=int, default=0,
                    help="pin each rank to K host CPUs (its share of an 8-rank node) and size the shuffle "
@@ -71,7 +86,10 @@ def parse():
                    help="the shuffle_windows mode (epoch e of an update shuffles from a fixed window of the "
                         "rank's RNG stream, so the host walks all epochs at once: bppo.h): auto = on for N>1 "
                         "(per-rank streams already depart from the reference's), off at N=1 (reference-exact)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -283,6 +301,46 @@ def steps_to_475(bppo, preset_over, max_steps, init_seed=0):
             "num_envs": N, "num_steps": T, "seconds": round(time.perf_counter() - t0, 2)}
 
 
+DUMP_SAMPLE_ROWS = 262144      # rollout-buffer rows kept per field (all of them when T*N is smaller)
+DUMP_METRICS = ("policy_loss", "value_loss", "entropy", "entropy_scaled", "approx_kl", "clip_fraction",
+                "explained_variance", "total_loss", "value_mean", "returns_mean", "adv_mean_raw", "adv_std_raw",
+                "adv_min_raw", "adv_max_raw", "value_error_mean", "value_error_std", "value_error_max",
+                "num_updates", "epochs_run", "episodes", "mean_return", "rng_word_pos")
+
+
+def dump_outputs(path, tr, last, rank):
+    """What a caller of the timed path holds after its last update, as <path>/<name>.npy
+    (rank r > 0 of an N > 1 run: <name>_rank<r>.npy), float32 / float64:
+      params            the network's parameters after the update (all of them)
+      metrics           the update's DUMP_METRICS, in that order (float64)
+      obs_norm, ret_norm   the normalizers' [mean.., M2.., count] / [mean, M2, count]
+      rollout_rows      the [t * N + env] rows sampled below (float64, exact)
+      observations, actions, rewards, dones, values, log_probs, advantages, returns
+                        the rollout buffer of the last update at those rows
+    The rows are a fixed seeded sample (DUMP_SAMPLE_ROWS of T*N, sorted), the same
+    for every run of one shape: ~12 MB at CfgB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    ctx = tr.ctx
+    TN = ctx.T * ctx.N
+    rows = np.arange(TN) if TN <= DUMP_SAMPLE_ROWS else \
+        np.sort(np.random.default_rng(0).choice(TN, DUMP_SAMPLE_ROWS, replace=False))
+    mean, m2, cnt = ctx.obs_norm()
+    out = {"params": tr.model.get_params(),
+           "metrics": np.array([float(last[k]) for k in DUMP_METRICS], np.float64),
+           "obs_norm": np.concatenate([mean, m2, [cnt]]),
+           "ret_norm": ctx.ret_norm()[0],
+           "rollout_rows": rows.astype(np.float64),
+           "observations": ctx.buffer("obs").reshape(TN, ctx.obs_dim)[rows],
+           "actions": ctx.buffer("actions", np.int32)[rows].astype(np.float32)}
+    for name in ("rewards", "dones", "values", "log_probs", "advantages", "returns"):
+        out[name] = ctx.buffer(name)[rows]
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+    return sorted(out)
+
+
 def selftest_main(args, world, rank):
     import torch
     import torch.distributed as dist
@@ -420,6 +478,7 @@ def main():
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = dump_outputs(args.dump_outputs, tr, last, rank) if args.dump_outputs else None
     tr.close()
     if rank != 0:
         dist.destroy_process_group()
@@ -462,8 +521,9 @@ def main():
                                       if mb_ex > 0 else None},
             "mean_all_launches_ms": round(mb_all, 4)}
     gae_loop_ms = phase["gae"] / args.steps
-    gae_ms = gae_loop_ms if args.no_gae_isolated else gae_isolated_ms(N, T)
-    gae_gbs = N * T * GAE_BYTES_PER_ELEM / (gae_ms * 1e-3) / 1e9
+    # (the isolated launches are a run of their own: --full only; a plain run reports no gae_roofline)
+    gae_ms = gae_isolated_ms(N, T) if args.full and not args.no_gae_isolated else gae_loop_ms
+    gae_gbs = N * T * GAE_BYTES_PER_ELEM / (gae_ms * 1e-3) / 1e9 if gae_ms > 0 else 0.0
     g_tr, g_src = traffic_for("k_gae_1p_seg", "k_gae.hip") if cfgB else (None, "not the profiled shape")
     gae_roof = {"bound": "hbm", "achieved": round(gae_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(gae_gbs / HBM_PEAK_GBS, 4), "traffic": g_tr, "traffic_unit": "B/launch",
@@ -501,7 +561,8 @@ def main():
            # shuffle engine walkers and word producers, the driver thread, HIP runtime)
            "host_cpu_ms_per_step": round(host_cpu_ms, 2),
            "host_cpu_ms_per_step_by_thread": host_cpu_threads,
-           "roofline": roof, "gae_roofline": gae_roof,
+           "full": args.full, "dumped_outputs": dumped,
+           "roofline": roof, "gae_roofline": gae_roof if args.full else None,
            "phase_ms_per_update": {k: round(v / args.steps, 3) for k, v in phase.items()},
            # the reference's perf/* scalars (main.rs:1092-1132) over the timed interval: the
            # job's env steps per second and the phases' summed device seconds (rollout = the
@@ -513,14 +574,14 @@ def main():
                                     "episodes", "explained_variance")},
            "explained_variance_note": "from f64 sums (the reference sums sequentially in f32, ~1e-3 off "
                                       "at 1e6 rows; INTEGRATION.md section 7)"}
-    if world == 1 and not args.no_learning:
+    if args.full and world == 1 and not args.no_learning:
         out["steps_to_475"] = {
             "window": "100 episodes (main.rs:842-853), checked after each rollout",
             "cfgB": steps_to_475(bppo, dict(num_envs=N, num_steps=T), max_steps=40 * N * T),
             "cartpole_toml": steps_to_475(bppo, dict(num_envs=32, num_steps=128), max_steps=1_000_000)}
     else:
         out["steps_to_475"] = None
-    out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(args)
+    out["cpu_baseline"] = cpu_baseline(args) if args.full and not args.no_cpu_baseline else None
     print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
