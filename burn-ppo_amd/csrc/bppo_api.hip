@@ -326,23 +326,12 @@ static bppo_status ctx_init(bppo_ctx *c, const bppo_config *cfg, int dev, void *
     TRY(dalloc(c, &c->d_perm_ep, TN * (size_t)cfg->num_epochs));
     TRY(dalloc(c, &c->d_inv_ep, TN * (size_t)cfg->num_epochs));
     TRY(dalloc(c, &c->d_advpart, (size_t)ADV_STREAM_BLOCKS * ADV_STREAM_MAXM * 4));
-    {
-        // BPPO_FY_ON_COPY=1 (A/B): the permutations on the shuffle engine's copy stream (one
-        // side stream instead of two; set after the engine's init below)
-        c->fy_shared = getenv("BPPO_FY_ON_COPY") && atoi(getenv("BPPO_FY_ON_COPY")) == 1;
-        if (!c->fy_shared) BPPO_HIP(c, make_side_stream(dev, &c->fy_stream));
-        for (int e = 0; e < cfg->num_epochs && e < SHUF_MAX_EPOCHS; e++)
-            BPPO_HIP(c, hipEventCreateWithFlags(&c->fy_ev[e], hipEventDisableTiming));
-        // the prep stream only when it is used (BPPO_PREP_SIDE=1): with this third low-priority
-        // stream created (even idle) every device-bound run took 13.1-13.6 instead of
-        // 10.9-11.2 ms per update, the phases outside the minibatch kernels 15-25 % slower;
-        // GPU_MAX_HW_QUEUES=8 did not remove it (profiles/r06y/, r06z/)
-        if (getenv("BPPO_PREP_SIDE") && atoi(getenv("BPPO_PREP_SIDE")) == 1) {
-            BPPO_HIP(c, make_side_stream(dev, &c->prep_stream));
-            BPPO_HIP(c, hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming));
-        }
-        BPPO_HIP(c, hipEventCreateWithFlags(&c->ev_env, hipEventDisableTiming));
-    }
+    // the context's only streams are the update stream, fy_stream and the engine's copy
+    // stream: a third low-priority stream, even idle, made every device-bound run
+    // 15-25 % slower outside the minibatch kernels (profiles/r06y/, r06z/)
+    BPPO_HIP(c, make_side_stream(dev, &c->fy_stream));
+    for (int e = 0; e < cfg->num_epochs && e < SHUF_MAX_EPOCHS; e++)
+        BPPO_HIP(c, hipEventCreateWithFlags(&c->fy_ev[e], hipEventDisableTiming));
     TRY(dalloc(c, &c->d_fy, 4 * TN));
     TRY(dalloc(c, &c->d_scan, TN / 8192 + 2));
     BPPO_HIP(c, fy_ranges_init(c->fyr, (uint32_t)TN));
@@ -360,7 +349,6 @@ static bppo_status ctx_init(bppo_ctx *c, const bppo_config *cfg, int dev, void *
     }
     BPPO_HIP(c, hipHostMalloc((void **)&c->h_red, sizeof(double) * (4 * 1024 + 64 + 2 * ROLL_HOST_WORDS),
                               hipHostMallocDefault));   // + two slots of the rollout's flags and episode partials
-    BPPO_HIP(c, hipHostGetDevicePointer((void **)&c->hd_red, c->h_red, 0));
     BPPO_HIP(c, hipEventCreateWithFlags(&c->ev_upd, hipEventDisableTiming));
     BPPO_HIP(c, hipEventRecord(c->ev_upd, c->stream));      // recorded once, so every wait on it is defined
     BPPO_HIP(c, hipEventCreateWithFlags(&c->ev_block, hipEventDisableTiming | hipEventBlockingSync));
@@ -374,10 +362,8 @@ static bppo_status ctx_init(bppo_ctx *c, const bppo_config *cfg, int dev, void *
     }
     c->rng_key = seed_key(cfg->seed);
     c->rng_pos = 0;
-    c->shuf.gate = c->ev_upd;     // before init: the engine thread starts in it
     TRY(c->shuf.init(dev, c->rng_key, cfg->rng_stream, (uint32_t)TN, cfg->num_epochs, TN * (uint64_t)c->A, c->err,
                      cfg->shuffle_windows != 0));
-    if (c->fy_shared) c->fy_stream = c->shuf.copy;
     c->on_mean.assign(c->D, 0.0); c->on_m2.assign(c->D, 0.0); c->on_count = 0;
     c->u_ret = c->d_ret; c->u_val = c->d_val;
     c->shaping_v.assign(1, cfg->reward_shaping_coef); c->shaping_s.assign(1, 0);   // Schedule::constant
@@ -410,7 +396,6 @@ extern "C" void bppo_destroy(bppo_ctx *c) {
     if (c->ev_copied) (void)hipEventDestroy(c->ev_copied);
     for (float *h : {c->h_ev_v, c->h_ev_r, c->h_ev_valid}) if (h) (void)hipHostFree(h);
     if (c->fy_stream) (void)hipStreamSynchronize(c->fy_stream);   // reads the engine's J buffers
-    if (c->prep_stream) (void)hipStreamSynchronize(c->prep_stream);
     c->shuf.shutdown();
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     wide_free(c);
@@ -433,10 +418,8 @@ extern "C" void bppo_destroy(bppo_ctx *c) {
     }
     for (auto &pr : c->mb_ev)
         for (hipEvent_t e : pr) if (e) (void)hipEventDestroy(e);
-    if (c->fy_stream && !c->fy_shared) { (void)hipStreamSynchronize(c->fy_stream); (void)hipStreamDestroy(c->fy_stream); }
+    if (c->fy_stream) { (void)hipStreamSynchronize(c->fy_stream); (void)hipStreamDestroy(c->fy_stream); }
     for (hipEvent_t e : c->fy_ev) if (e) (void)hipEventDestroy(e);
-    if (c->prep_stream) (void)hipStreamDestroy(c->prep_stream);
-    for (hipEvent_t e : {c->ev_env, c->ev_prep}) if (e) (void)hipEventDestroy(e);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -543,10 +526,8 @@ extern "C" bppo_status bppo_rng_from_seed(bppo_ctx *c, const uint8_t *seed) {
     c->rng_pos = 0;
     c->shuf_slot = -1;
     const size_t TN = (size_t)c->T * c->N;
-    c->shuf.gate = c->ev_upd;
     TRY(c->shuf.init(c->dev, c->rng_key, c->cfg.rng_stream, (uint32_t)TN, c->cfg.num_epochs, TN * (uint64_t)c->A, c->err,
                      c->cfg.shuffle_windows != 0));
-    if (c->fy_shared) c->fy_stream = c->shuf.copy;
     return BPPO_OK;
 }
 
@@ -826,15 +807,9 @@ static bppo_status collect_enqueue(bppo_ctx *c, bool summary) {
     int32_t *hv = reinterpret_cast<int32_t *>(roll_host(c, c->coll_slot));     // pinned
     if (summary) {
         // the summary kernel writes the episode count, the error flags and its partial sums in
-        // the host slot's layout: into d_ep_sum and ONE copy (r05: three), or with
-        // BPPO_ZERO_COPY=1 straight into the pinned slot (A/B: slower, gaps after the kernels
-        // that write host memory -- profiles/r06t/)
-        if (zero_copy()) {
-            TRY(launch_episode_summary(c, c->hd_red + (roll_host(c, c->coll_slot) - c->h_red)));
-        } else {
-            TRY(launch_episode_summary(c, c->d_ep_sum));
-            BPPO_HIP(c, hipMemcpyAsync(hv, c->d_ep_sum, sizeof(double) * ROLL_HOST_WORDS, hipMemcpyDeviceToHost, c->stream));
-        }
+        // the host slot's layout: into d_ep_sum and ONE copy (r05: three)
+        TRY(launch_episode_summary(c, c->d_ep_sum));
+        BPPO_HIP(c, hipMemcpyAsync(hv, c->d_ep_sum, sizeof(double) * ROLL_HOST_WORDS, hipMemcpyDeviceToHost, c->stream));
     } else {
         BPPO_HIP(c, hipMemcpyAsync(&hv[0], c->d_ep_count, 4, hipMemcpyDeviceToHost, c->stream));
         BPPO_HIP(c, hipMemcpyAsync(&hv[1], c->d_err, 4, hipMemcpyDeviceToHost, c->stream));

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 #include <thread>
@@ -138,9 +139,7 @@ struct ShuffleEngine {
     uint64_t stream = 0;
     uint64_t gap = 0;                             // words between an update's last shuffle and the next update's first
     uint64_t win = 0;                             // shuffle_windows: epoch e starts at job start + e * win (0: chained)
-    bool keep_guess = true;                       // keep the nearest guessed walks beside an exact continuation
     bool pair = false;                            // windowed: worker 2m walks epochs 2m and 2m+1 interleaved
-    bool win_producers = false;                   // windowed: host word producers (default: the walks make their words)
     bool win_gpu_words = false;                   // windowed: the job's GPU words are copied to the host (SDMA)
     hipStream_t d2h = nullptr;                    // those copies
     hipEvent_t words_made = nullptr;
@@ -204,10 +203,6 @@ struct ShuffleEngine {
     hipEvent_t ev[2][SHUF_MAX_EPOCHS] = {};
     bool ev_used[2][SHUF_MAX_EPOCHS] = {};
     hipStream_t copy = nullptr;
-    // the caller's end-of-update event (bppo_ctx::ev_upd): with BPPO_XJ_GATE the J expansions
-    // wait for the update enqueued last, so a job the walks finished early is not expanded
-    // beside that update's minibatches (1: every epoch, 2: epochs after the first)
-    hipEvent_t gate = nullptr;
     double walk_ms[2][SHUF_MAX_EPOCHS] = {};
     int coalesced[2][SHUF_MAX_EPOCHS] = {};       // checkpoints walked before meeting a speculative walk (-1: none)
     std::atomic<uint64_t> spec_words{0}, true_words{0};   // words walked since the caller last read them
@@ -215,7 +210,6 @@ struct ShuffleEngine {
     bppo_status init(int device, const Key8 &key, uint64_t stream, uint32_t n_, int epochs_, uint64_t gap_,
                      std::string &err, bool windows = false);
     bool run_windowed(int slot, uint64_t start);   // one job of independent epoch walks (false: cancelled)
-    void xj_gate_wait(int e);                      // BPPO_XJ_GATE: copy waits on `gate` before epoch e's expansion
     uint64_t job_end(int slot) const { return win ? slot_start[slot] + (uint64_t)epochs * win : end_pos[slot][epochs - 1]; }
     // a HIP call of the engine's own thread that failed (its uploads, J expansions, events):
     // the first one is kept and the caller's next wait on the engine reports it
@@ -324,13 +318,7 @@ struct bppo_ctx {
     uint32_t *d_inv_ep = nullptr;     // [epochs][TN] their inverses (row -> shuffled position)
     double *d_advpart = nullptr;      // k_adv_stream block partials
     hipStream_t fy_stream = nullptr;
-    bool fy_shared = false;           // BPPO_FY_ON_COPY=1 (A/B): fy_stream IS the engine's copy stream
     hipEvent_t fy_ev[bppo::SHUF_MAX_EPOCHS] = {};
-    // CfgB 64-lane rollout: its Gumbel words and reset pool made on prep_stream as soon as the
-    // previous env-state writer (ev_env: the last rollout / reset / vecenv step) finished, i.e.
-    // beside the previous update's minibatches, not between them and the rollout (r06)
-    hipStream_t prep_stream = nullptr;
-    hipEvent_t ev_env = nullptr, ev_prep = nullptr;
     int fy_slot = -1, fy_done = 0;    // engine slot whose epochs [0, fy_done) are enqueued on fy_stream
     uint32_t *d_fy = nullptr;         // Fisher-Yates scratch [4][TN]: count/offset, bucket, succ, fw
     uint32_t *d_scan = nullptr;       // scan block sums
@@ -339,8 +327,6 @@ struct bppo_ctx {
     // scratch
     double *d_red = nullptr;          // reduction scratch
     double *h_red = nullptr;          // pinned mirror
-    double *hd_red = nullptr;         // h_red's device address (BPPO_ZERO_COPY=1: kernels write their
-                                      // few host-bound results there instead of a D2H copy)
     float *h_rows = nullptr;          // pinned: the update's metric rows
     float *d_mb_stats = nullptr;      // advantage [mean, std, min, max] of each minibatch of the epoch [M][4]
     float *d_mb_cur = nullptr;        // the current minibatch's row of d_mb_stats
@@ -461,6 +447,12 @@ struct bppo_ctx {
 };
 
 namespace bppo {
+// runtime switches: every BPPO_* variable is read through these two
+inline bool env_set(const char *name) { return getenv(name) != nullptr; }               // present, any value
+inline int env_int(const char *name, int dflt) {                                         // atoi(value), dflt when unset
+    const char *v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
 // kernel-phase timer slots
 enum { TM_ROLLOUT = 0, TM_GAE = 1, TM_UPDATE = 2, TM_FWDBWD = 3, TM_RETNORM = 4, TM_SHUFFLE = 5,
        TM_ADAM = 6, TM_BOOT = 7 };
@@ -477,12 +469,6 @@ bppo_status launch_cartpole_vecenv_step(bppo_ctx *c, const int32_t *d_actions, f
 bppo_status launch_cartpole_observe(bppo_ctx *c, float *d_obs_out);
 bppo_status launch_obs_norm_merge(bppo_ctx *c);
 bppo_status launch_episode_summary(bppo_ctx *c, double *host_slot);
-// BPPO_ZERO_COPY=1 (A/B): the episode summary and the explained-variance sums written into
-// pinned host memory by their kernels instead of copied after them
-inline bool zero_copy() {
-    static const bool z = getenv("BPPO_ZERO_COPY") && atoi(getenv("BPPO_ZERO_COPY")) == 1;
-    return z;
-}
 bppo_status launch_obs_norm_rows(bppo_ctx *c, int rows, float *x, int ld, float *raw);
 bppo_status launch_obs_norm_rows_on(bppo_ctx *c, int rows, float *x, int ld, float *raw, const double *on);
 bppo_status launch_bootstrap(bppo_ctx *c, const double *mean, const double *sd, int norm_on);

@@ -169,7 +169,6 @@ struct GemmArgs {
     // WG: partial slab [split][M][N] and column sums [split][N]; rows of the
     // reduction per split (float, or double for k_gemm_wg64)
     float *part; float *colsum; int k_per_split;
-    int xcd;                     // XCD-aware tile order (tile_of)
     int avec, bvec;              // k_gemm_split: operand 16-B aligned with ld % 4 == 0 (float4 loads)
 };
 
@@ -179,13 +178,13 @@ enum { GEMM_FWD = 0, GEMM_DX = 1, GEMM_WG = 2 };
 // XCD b % 8), each with its own L2.  Dealt in grid order, the N-tiles of one row tile (which
 // read the same A rows) land on different XCDs and every XCD fetches those rows from HBM.
 // Remapped, XCD j runs the logical tiles [j T/8, (j+1) T/8): consecutive tiles -- the N-tiles
-// of a row tile, the tiles of one split -- share an L2.  g.xcd = 0: grid order.
+// of a row tile, the tiles of one split -- share an L2.  (Grids of a multiple of 8 blocks.)
 struct Tile { int x, y, z; };
-__device__ __forceinline__ Tile tile_of(int xcd) {
+__device__ __forceinline__ Tile tile_of() {
     const unsigned gx = gridDim.x, gy = gridDim.y;
     const unsigned total = gx * gy * gridDim.z;
     unsigned b = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-    if (xcd && total % 8 == 0) b = (b % 8) * (total / 8) + b / 8;
+    if (total % 8 == 0) b = (b % 8) * (total / 8) + b / 8;
     return Tile{(int)(b % gx), (int)((b / gx) % gy), (int)(b / (gx * gy))};
 }
 
@@ -260,7 +259,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm(GemmArgs g) {
     __shared__ float sB[2][GBK * S::BPAD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
-    const Tile tl = tile_of(g.xcd);
+    const Tile tl = tile_of();
     const int m0 = tl.y * BM, n0 = tl.x * BN;
     int kbeg = 0, kend = g.K;
     if constexpr (MODE == GEMM_WG) {
@@ -531,7 +530,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm_split(GemmArgs g) {
     __shared__ __attribute__((aligned(16))) __bf16 sB[3 * BN * SKP];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
-    const Tile tl = tile_of(g.xcd);
+    const Tile tl = tile_of();
     const int m0 = tl.y * BM, n0 = tl.x * BN;
     int kbeg = 0, kend = g.K;
     if constexpr (MODE == GEMM_WG) {
@@ -630,7 +629,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm_wg64(GemmArgs g) {
     __shared__ float sB[2][GBK * BPAD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
-    const Tile tl = tile_of(g.xcd);
+    const Tile tl = tile_of();
     const int m0 = tl.y * BM, n0 = tl.x * BN;
     const int kbeg = tl.z * g.k_per_split, kend = min(g.K, kbeg + g.k_per_split);
     typename std::conditional<AK != 0, ConvLoader<BM, false>, TileLoader<BM, false>>::type la;
@@ -819,15 +818,9 @@ static hipError_t tanh_inplace(hipStream_t st, float *y, int M, int cols, int ld
 }
 
 // -------------------------------------------------------------- launchers --
-// BPPO_GEMM_XCD=0: grid-order tiles (A/B of the XCD-aware order)
-static int gemm_xcd() {
-    static const int v = getenv("BPPO_GEMM_XCD") ? atoi(getenv("BPPO_GEMM_XCD")) : 1;
-    return v;
-}
 template <int MODE, int BM, int BN, int WM, int WN, int AK>
-static hipError_t launch(GemmArgs g, int splits, hipStream_t st) {
+static hipError_t launch(const GemmArgs &g, int splits, hipStream_t st) {
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, splits);
-    g.xcd = gemm_xcd();
     hipLaunchKernelGGL((k_gemm<MODE, BM, BN, WM, WN, AK>), grid, dim3(256), 0, st, g);
     return hipGetLastError();
 }
@@ -836,7 +829,6 @@ static bool vec_ok(const float *p, int ld) { return ((uintptr_t)p & 15) == 0 && 
 template <int MODE, int BM, int BN, int WM, int WN>
 static hipError_t launch_split(GemmArgs g, int splits, hipStream_t st) {
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, splits);
-    g.xcd = gemm_xcd();
     g.avec = vec_ok(g.A, g.lda); g.bvec = vec_ok(g.B, g.ldb);
     hipLaunchKernelGGL((k_gemm_split<MODE, BM, BN, WM, WN>), grid, dim3(256), 0, st, g);
     return hipGetLastError();
@@ -849,9 +841,8 @@ static hipError_t launch_split_by_width(const GemmArgs &g, int splits, hipStream
 }
 
 template <int BM, int BN, int AK>
-static hipError_t launch64(GemmArgs g, int splits, hipStream_t st) {
+static hipError_t launch64(const GemmArgs &g, int splits, hipStream_t st) {
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, splits);
-    g.xcd = gemm_xcd();
     hipLaunchKernelGGL((k_gemm_wg64<BM, BN, AK>), grid, dim3(256), 0, st, g);
     return hipGetLastError();
 }
@@ -927,8 +918,7 @@ hipError_t gemm_dx(hipStream_t st, int M, int N, int K, const float *dZ, int ldz
 
 int gemm_wg_splits(int Kin, int N, int rows) {
     const int tiles = ((Kin + 127) / 128) * ((N + (N <= 32 ? 31 : N <= 64 ? 63 : 127)) / (N <= 32 ? 32 : N <= 64 ? 64 : 128));
-    // ~2048 blocks (BPPO_WG_BLOCKS: another target, for A/B runs of the slab traffic)
-    static const int target = getenv("BPPO_WG_BLOCKS") ? std::max(1, atoi(getenv("BPPO_WG_BLOCKS"))) : 2048;
+    constexpr int target = 2048;                         // ~2048 blocks
     int s = (target + tiles - 1) / tiles;
     const int max_by_rows = (rows + 1023) / 1024;        // >= 1024 rows per split
     if (s > max_by_rows) s = max_by_rows;

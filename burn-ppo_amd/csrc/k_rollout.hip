@@ -234,13 +234,13 @@ __global__ void __launch_bounds__(256) k_cartpole_rollout(RolloutArgs a) {
 // instruction writes 256 consecutive floats (a thread's own 16 words would be
 // a 64-B-strided store per word)
 constexpr int GUM_THREADS = 256;
-// zero0 / zero1 (optional): the rollout's episode counter and error flags, set to 0 here
+// zero0 / zero1: the rollout's episode counter and error flags, set to 0 here
 // (one store each) instead of by two fill launches ahead of it
 __global__ void __launch_bounds__(GUM_THREADS) k_gumbel_words(Key8 key, uint64_t stream, uint64_t base,
                                                               uint64_t count, float *__restrict__ g,
                                                               int32_t *zero0, int32_t *zero1) {
     __shared__ float tile[16 * GUM_THREADS + GUM_THREADS / 2];
-    if (zero0 && blockIdx.x == 0 && threadIdx.x == 0) { *zero0 = 0; *zero1 = 0; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { *zero0 = 0; *zero1 = 0; }
     const uint64_t blk0 = (base >> 4) + blockIdx.x * (uint64_t)GUM_THREADS;
     const uint64_t b = blk0 + threadIdx.x, wb = blk0 * 16;
     if (b * 16 < base + count) {
@@ -966,29 +966,18 @@ bppo_status launch_cartpole_reset(bppo_ctx *c) {
                        c->cfg.env_seed_base, c->d_cp, c->d_steps, c->d_env_pos, c->d_ep_ret,
                        c->d_ep_len, nullptr);
     TRY(launch_check(c, __func__));
-    if (c->ev_env) BPPO_HIP(c, hipEventRecord(c->ev_env, c->stream));   // env state written
     return BPPO_OK;
 }
 
-static bppo_status launch_cartpole_rollout_kernels(bppo_ctx *c, uint64_t base_pos, int norm_on);
-// every CartPole rollout variant, then ev_env: the env state it wrote (and the 64-lane
-// kernel's Gumbel words / reset pool it read) -- what the next rollout's prep_stream waits for
+// every CartPole rollout variant
 bppo_status launch_cartpole_rollout(bppo_ctx *c, uint64_t base_pos, const double *, const double *,
                                     int norm_on) {
-    const bppo_status s = launch_cartpole_rollout_kernels(c, base_pos, norm_on);
-    if (s == BPPO_OK && c->ev_env) BPPO_HIP(c, hipEventRecord(c->ev_env, c->stream));
-    return s;
-}
-
-static bppo_status launch_cartpole_rollout_kernels(bppo_ctx *c, uint64_t base_pos, int norm_on) {
     const int h = c->cfg.hidden_size, nl = c->cfg.num_hidden;
-    // the episode counter and error flags at 0 before the rollout: in the Gumbel kernel when it
-    // runs on the update stream (below), else two fills here
-    static const bool prep_side = getenv("BPPO_PREP_SIDE") && atoi(getenv("BPPO_PREP_SIDE")) == 1;
-    const bool lanes64 = !(getenv("BPPO_ROLLOUT_LANES64") && atoi(getenv("BPPO_ROLLOUT_LANES64")) == 0);
+    // the episode counter and error flags at 0 before the rollout: in the Gumbel kernel
+    // where it runs (below), else two fills here
+    const bool lanes64 = env_int("BPPO_ROLLOUT_LANES64", 1) != 0;
     const bool gum_path = h == 64 && nl == 2 && c->cfg.relu && c->d_gumbel;
-    const bool side = gum_path && lanes64 && prep_side && c->prep_stream && c->ev_env && c->ev_prep;
-    if (!gum_path || side) {
+    if (!gum_path) {
         BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
         BPPO_HIP(c, hipMemsetAsync(c->d_err, 0, 4, c->stream));
     }
@@ -1012,24 +1001,16 @@ static bppo_status launch_cartpole_rollout_kernels(bppo_ctx *c, uint64_t base_po
         // the update's packed rows (obs, action, log-prob, value) written by the rollout
         // itself; GAE adds advantage and return, so k_pack_rows is not needed (PopArt
         // trains on normalized values computed at update start: packed there instead)
-        if (c->d_rowA && !c->cfg.normalize_values && !getenv("BPPO_NO_FUSED_PACK")) {
+        if (c->d_rowA && !c->cfg.normalize_values && !env_set("BPPO_NO_FUSED_PACK")) {
             a.rows = c->d_rowA;
             c->rows_from_rollout = true;
         }
         // Gumbel noise for every (t, env, action) first, then the MFMA rollout
         const uint64_t count = (uint64_t)c->T * c->N * 2;
         const uint64_t blocks = ((base_pos + count + 15) >> 4) - (base_pos >> 4);
-        // BPPO_PREP_SIDE=1 (r06, A/B): the 64-lane rollout's inputs (Gumbel words, reset pool)
-        // on prep_stream, which waits only for the last env-state writer (the previous
-        // rollout), so they run beside the previous update instead of between its last
-        // minibatch and this rollout.  Kernel traces: the gap before the rollout 285-607 ->
-        // 121-295 us, but the update's minibatches 0.2-0.45 ms longer beside them (update span
-        // 11.04 / 12.39 vs 11.36 / 12.24 ms, profiles/r06p/): off by default
-        hipStream_t ps = side ? c->prep_stream : c->stream;
-        if (side) BPPO_HIP(c, hipStreamWaitEvent(ps, c->ev_env, 0));
-        hipLaunchKernelGGL(k_gumbel_words, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, ps, c->rng_key,
-                           (uint64_t)c->cfg.rng_stream, base_pos, count, c->d_gumbel,
-                           side ? nullptr : c->d_ep_count, side ? nullptr : (int32_t *)c->d_err);
+        hipLaunchKernelGGL(k_gumbel_words, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, c->stream,
+                           c->rng_key, (uint64_t)c->cfg.rng_stream, base_pos, count, c->d_gumbel, c->d_ep_count,
+                           (int32_t *)c->d_err);
         TRY(launch_check(c, "k_gumbel_words"));
         // default: the 64-lane kernel (269 registers and 84 KB of LDS per 4-wave block, so
         // the side-stream Fisher-Yates passes still share its CUs): device-bound A/B
@@ -1042,10 +1023,9 @@ static bppo_status launch_cartpole_rollout_kernels(bppo_ctx *c, uint64_t base_po
         } else {
             const int waves = (c->N + 63) / 64;
             // BPPO_RESET_POOL_K (tests): a shorter pool (exercises the in-kernel fallback), 0: none
-            int pk = RPOOL_K;
-            if (const char *v = getenv("BPPO_RESET_POOL_K")) pk = std::max(0, std::min(RPOOL_K, atoi(v)));
+            const int pk = std::max(0, std::min(RPOOL_K, env_int("BPPO_RESET_POOL_K", RPOOL_K)));
             if (c->d_rpool && pk > 0) {
-                hipLaunchKernelGGL(k_reset_pool, dim3((c->N + 255) / 256), dim3(256), 0, ps, c->N, pk,
+                hipLaunchKernelGGL(k_reset_pool, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, c->N, pk,
                                    c->cfg.env_seed_base, (const uint64_t *)c->d_env_pos, c->d_rpool, c->d_rpos);
                 TRY(launch_check(c, "k_reset_pool"));
                 a.rpool = c->d_rpool; a.rpos = c->d_rpos; a.rpool_k = pk;
@@ -1055,10 +1035,6 @@ static bppo_status launch_cartpole_rollout_kernels(bppo_ctx *c, uint64_t base_po
             if (!d_st) BPPO_HIP(c, hipMalloc((void **)&d_st, sizeof(unsigned long long) * (size_t)waves * RO_NSEG));
             a.stamps = d_st;
 #endif
-            if (side) {
-                BPPO_HIP(c, hipEventRecord(c->ev_prep, ps));
-                BPPO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prep, 0));
-            }
             hipLaunchKernelGGL(k_cartpole_rollout_mfma64, dim3((waves + mmr::WAVES - 1) / mmr::WAVES),
                                dim3(64 * mmr::WAVES), 0, c->stream, a, (const float *)c->d_gumbel);
 #ifdef BPPO_RO_STAMPS
@@ -1124,7 +1100,6 @@ bppo_status launch_cartpole_vecenv_step(bppo_ctx *c, const int32_t *d_actions, f
                        c->d_ep_len, d_actions, d_rew, d_done, d_obs_out, c->d_eps, c->d_ep_count,
                        c->eps_cap);
     TRY(launch_check(c, __func__));
-    if (c->ev_env) BPPO_HIP(c, hipEventRecord(c->ev_env, c->stream));   // env state written
     return BPPO_OK;
 }
 

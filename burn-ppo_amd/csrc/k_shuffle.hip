@@ -13,14 +13,16 @@
 // order each bucket, read succ/fw off neighbours, and follow fw chains (mean
 // length ~1, max ~20 at n = 2^23).  Bit-exact; no host swaps.
 //
-// Two bucketings.  The direct one counts and scatters with one global atomic
-// per step.  The ranged one (n >= FYB_MIN_N: the per-epoch shuffles of a
-// context) partitions the steps into target ranges of equal expected load —
-// J[i] is uniform on [0, i], so E#{i : J[i] < x} = x (1 + ln(n/x)) — with LDS
-// histograms, each block reserving its slots in a range's fixed-capacity slice with
-// one global atomic per (block, range), then sorts and links each range in LDS.  A
-// range over its capacity (inputs far from uniform) raises a flag and the direct
-// path runs after it, gated on that flag, so any J gives the same result.
+// Two bucketings.  The direct one (n < FYB_MIN_N) counts and scatters with one
+// global atomic per step, in seven launches.  The ranged one (n >= FYB_MIN_N: the
+// per-epoch shuffles of a context) partitions the steps into target ranges of
+// equal expected load — J[i] is uniform on [0, i], so E#{i : J[i] < x} =
+// x (1 + ln(n/x)) — with LDS histograms, each block reserving its slots in a
+// range's fixed-capacity slice with one global atomic per (block, range)
+// (k_fyb_bucket), then sorts and links each range in LDS (k_fyb_link).  A range
+// over its capacity (inputs far from uniform) raises a flag; k_fy_final then skips
+// and k_fy_direct_block, the direct bucketing in one block, runs instead, so any
+// J gives the same result.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -44,17 +46,11 @@ constexpr int FYB_COARSE = 11;         // coarse index: first range of each 2^11
 constexpr int FYB_LINK_THREADS = 512;
 constexpr size_t FYB_LDS_MAX = 120 * 1024;
 
-// gate == nullptr: always run; else run only when *gate != 0 (a range overflowed)
-#define FY_GATE(g) \
-    if ((g) && *(g) == 0u) return
-
-__global__ void __launch_bounds__(256) k_fy_zero(uint32_t *p, uint32_t n, const uint32_t *gate) {
-    FY_GATE(gate);
+__global__ void __launch_bounds__(256) k_fy_zero(uint32_t *p, uint32_t n) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0u;
 }
 
-__global__ void __launch_bounds__(256) k_fy_count(const uint32_t *J, uint32_t n, uint32_t *cnt, const uint32_t *gate) {
-    FY_GATE(gate);
+__global__ void __launch_bounds__(256) k_fy_count(const uint32_t *J, uint32_t n, uint32_t *cnt) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
         atomicAdd(&cnt[J[i]], 1u);
 }
@@ -86,9 +82,7 @@ __device__ __forceinline__ uint32_t block_exclusive_u32(uint32_t v, uint32_t *sh
     return wpre + x - v;
 }
 
-__global__ void __launch_bounds__(SCAN_B) k_scan_tiles(const uint32_t *in, uint32_t n, uint32_t *tile_sum,
-                                                       const uint32_t *gate) {
-    FY_GATE(gate);
+__global__ void __launch_bounds__(SCAN_B) k_scan_tiles(const uint32_t *in, uint32_t n, uint32_t *tile_sum) {
     __shared__ uint32_t sh[SCAN_B / 64];
     const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_IPT;
     uint32_t s = 0;
@@ -99,8 +93,7 @@ __global__ void __launch_bounds__(SCAN_B) k_scan_tiles(const uint32_t *in, uint3
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = tot;
 }
 
-__global__ void __launch_bounds__(SCAN_B) k_scan_sums(uint32_t *tile_sum, uint32_t ntiles, const uint32_t *gate) {
-    FY_GATE(gate);
+__global__ void __launch_bounds__(SCAN_B) k_scan_sums(uint32_t *tile_sum, uint32_t ntiles) {
     __shared__ uint32_t sh[SCAN_B / 64];
     uint32_t carry = 0;
     for (uint32_t b0 = 0; b0 < ntiles; b0 += SCAN_B) {
@@ -115,8 +108,7 @@ __global__ void __launch_bounds__(SCAN_B) k_scan_sums(uint32_t *tile_sum, uint32
 
 // out may alias in (each thread reads its elements before writing them)
 __global__ void __launch_bounds__(SCAN_B) k_scan_apply(const uint32_t *in, uint32_t n, const uint32_t *tile_pre,
-                                                       uint32_t *out, const uint32_t *gate) {
-    FY_GATE(gate);
+                                                       uint32_t *out) {
     __shared__ uint32_t sh[SCAN_B / 64];
     const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_IPT;
     uint32_t v[SCAN_IPT], s = 0;
@@ -131,18 +123,16 @@ __global__ void __launch_bounds__(SCAN_B) k_scan_apply(const uint32_t *in, uint3
     }
 }
 
-static void launch_scan(const uint32_t *in, uint32_t n, uint32_t *scan, uint32_t *out, const uint32_t *gate,
-                        hipStream_t st) {
+static void launch_scan(const uint32_t *in, uint32_t n, uint32_t *scan, uint32_t *out, hipStream_t st) {
     const uint32_t ntiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(SCAN_B), 0, st, in, n, scan, gate);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_B), 0, st, scan, ntiles, gate);
-    hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(SCAN_B), 0, st, in, n, scan, out, gate);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(SCAN_B), 0, st, in, n, scan);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_B), 0, st, scan, ntiles);
+    hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(SCAN_B), 0, st, in, n, scan, out);
 }
 
 // scatter step indices into their target's bucket (order inside a bucket fixed later)
 __global__ void __launch_bounds__(256) k_fy_scatter(const uint32_t *J, uint32_t n, const uint32_t *off,
-                                                    uint32_t *cnt, uint32_t *bucket, const uint32_t *gate) {
-    FY_GATE(gate);
+                                                    uint32_t *cnt, uint32_t *bucket) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t j = J[i];
         const uint32_t k = atomicSub(&cnt[j], 1u) - 1u;
@@ -152,8 +142,7 @@ __global__ void __launch_bounds__(256) k_fy_scatter(const uint32_t *J, uint32_t 
 
 // one thread per target j: sort its bucket, link successors, first writer fw(j)
 __global__ void __launch_bounds__(256) k_fy_link(uint32_t n, const uint32_t *off, uint32_t *bucket,
-                                                 uint32_t *succ, uint32_t *fw, const uint32_t *gate) {
-    FY_GATE(gate);
+                                                 uint32_t *succ, uint32_t *fw) {
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
         const uint32_t b = off[j], e = j + 1 < n ? off[j + 1] : n;
         for (uint32_t a = b + 1; a < e; a++) {              // insertion sort (mean size 1)
@@ -208,64 +197,14 @@ __device__ __forceinline__ void fyb_load_tab(const FyTab &t, uint32_t *sx, uint3
     for (int k = threadIdx.x; k < t.ncb; k += blockDim.x) scb[k] = t.cb[k];
 }
 
-// pass 1: per-block range histogram of a contiguous chunk of steps, range-major
-// H[b][blk] so that one exclusive scan gives every (range, block) write offset
+// passes 1 + 2, one block per contiguous chunk of steps: the block's range histogram in LDS,
+// then one global atomic per (block, range) reserves the block's slots in the range's
+// fixed-capacity slice of P ([nb][FYB_CAP]; cursor[b] ends as range b's step count), then the
+// chunk's steps are scattered into them (its J re-read, an L2 hit).  The slot order inside a
+// range is free: k_fyb_link sorts it.  A range past FYB_CAP raises the flag (its excess is not
+// written).  FYB_U targets are loaded before their counts (a plain loop waits on each load in
+// turn; the counts do not depend on the order)
 constexpr int FYB_U = 8;
-__global__ void __launch_bounds__(FYB_THREADS) k_fyb_hist(const uint32_t *J, uint32_t n, uint32_t chunk, FyTab t,
-                                                          uint32_t *H, uint32_t *flag) {
-    extern __shared__ uint32_t fsm[];
-    uint32_t *sx = fsm, *scb = sx + t.nb + 1, *hist = scb + t.ncb;
-    fyb_load_tab(t, sx, scb);
-    for (int k = threadIdx.x; k < t.nb; k += blockDim.x) hist[k] = 0u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *flag = 0u;
-    __syncthreads();
-    const uint32_t i0 = blockIdx.x * chunk, i1 = min(n, i0 + chunk);
-    // FYB_U targets loaded before their counts (the plain loop waited on each load in turn;
-    // the counts do not depend on the order)
-    uint32_t i = i0 + threadIdx.x;
-    for (; i + (FYB_U - 1) * blockDim.x < i1; i += FYB_U * blockDim.x) {
-        uint32_t jv[FYB_U];
-#pragma unroll
-        for (int u = 0; u < FYB_U; u++) jv[u] = J[i + u * blockDim.x];
-#pragma unroll
-        for (int u = 0; u < FYB_U; u++) atomicAdd(&hist[fyb_range(jv[u], sx, scb)], 1u);
-    }
-    for (; i < i1; i += blockDim.x) atomicAdd(&hist[fyb_range(J[i], sx, scb)], 1u);
-    __syncthreads();
-    for (int k = threadIdx.x; k < t.nb; k += blockDim.x) H[(size_t)k * gridDim.x + blockIdx.x] = hist[k];
-}
-
-// pass 2: (step, target) pairs into their range's slice (order inside a slice is
-// fixed by the link pass)
-__global__ void __launch_bounds__(FYB_THREADS) k_fyb_scatter(const uint32_t *J, uint32_t n, uint32_t chunk, FyTab t,
-                                                             const uint32_t *H, uint2 *P) {
-    extern __shared__ uint32_t fsm[];
-    uint32_t *sx = fsm, *scb = sx + t.nb + 1, *pos = scb + t.ncb;
-    fyb_load_tab(t, sx, scb);
-    for (int k = threadIdx.x; k < t.nb; k += blockDim.x) pos[k] = H[(size_t)k * gridDim.x + blockIdx.x];
-    __syncthreads();
-    const uint32_t i0 = blockIdx.x * chunk, i1 = min(n, i0 + chunk);
-    uint32_t i = i0 + threadIdx.x;                // (the slot order inside a range is free: see above)
-    for (; i + (FYB_U - 1) * blockDim.x < i1; i += FYB_U * blockDim.x) {
-        uint32_t jv[FYB_U];
-#pragma unroll
-        for (int u = 0; u < FYB_U; u++) jv[u] = J[i + u * blockDim.x];
-#pragma unroll
-        for (int u = 0; u < FYB_U; u++)
-            P[atomicAdd(&pos[fyb_range(jv[u], sx, scb)], 1u)] = make_uint2(i + u * blockDim.x, jv[u]);
-    }
-    for (; i < i1; i += blockDim.x) {
-        const uint32_t j = J[i];
-        P[atomicAdd(&pos[fyb_range(j, sx, scb)], 1u)] = make_uint2(i, j);
-    }
-}
-
-// passes 1 + 2 in one launch (r06; was k_fyb_hist, a three-launch scan of the [range][block]
-// counts and k_fyb_scatter): the block's range histogram in LDS, then one global atomic per
-// (block, range) reserves the block's slots in the range's fixed-capacity slice of P
-// ([nb][FYB_CAP]; cursor[b] ends as range b's step count), then the chunk's steps are
-// scattered into them (its J re-read, an L2 hit).  The slot order inside a range is free:
-// k_fyb_link sorts it.  A range past FYB_CAP raises the flag (its excess is not written)
 __global__ void __launch_bounds__(FYB_THREADS) k_fyb_bucket(const uint32_t *J, uint32_t n, uint32_t chunk, FyTab t,
                                                             uint32_t *cursor, uint2 *P, uint32_t *flag) {
     extern __shared__ uint32_t fsm[];
@@ -314,11 +253,9 @@ __global__ void __launch_bounds__(FYB_THREADS) k_fyb_bucket(const uint32_t *J, u
 }
 
 // pass 3: one block per range — counting sort by target in LDS, each target's
-// steps ordered by index, then succ / fw exactly as k_fy_link.  Ranges come as a
-// [range][block] offset table H (e0 = H[b][0]) or, cursor != nullptr, as fixed slices
+// steps ordered by index, then succ / fw exactly as k_fy_link.  Range b is the fixed slice
 // P[b * FYB_CAP ...] of cursor[b] steps (cursor[b] reset to 0 for the next permutation)
-__global__ void __launch_bounds__(FYB_LINK_THREADS) k_fyb_link(uint32_t n, FyTab t, const uint32_t *H, int nblk,
-                                                               const uint2 *P, uint32_t *succ, uint32_t *fw,
+__global__ void __launch_bounds__(FYB_LINK_THREADS) k_fyb_link(FyTab t, const uint2 *P, uint32_t *succ, uint32_t *fw,
                                                                uint32_t *flag, uint32_t *cursor) {
     __shared__ uint32_t ent_i[FYB_CAP];
     __shared__ uint16_t ent_t[FYB_CAP];
@@ -327,16 +264,9 @@ __global__ void __launch_bounds__(FYB_LINK_THREADS) k_fyb_link(uint32_t n, FyTab
     __shared__ uint32_t srt[FYB_CAP];
     __shared__ uint32_t sh[FYB_LINK_THREADS / 64];
     const int b = blockIdx.x;
-    uint32_t e0, cnt;
-    if (cursor) {
-        e0 = (uint32_t)b * FYB_CAP;
-        cnt = cursor[b];
-        __syncthreads();                      // every thread has read the count
-        if (threadIdx.x == 0) cursor[b] = 0u;
-    } else {
-        e0 = H[(size_t)b * nblk];
-        cnt = (b + 1 < t.nb ? H[(size_t)(b + 1) * nblk] : n) - e0;
-    }
+    const uint32_t e0 = (uint32_t)b * FYB_CAP, cnt = cursor[b];
+    __syncthreads();                          // every thread has read the count
+    if (threadIdx.x == 0) cursor[b] = 0u;
     const uint32_t lo = t.x[b], R = t.x[b + 1] - lo;
     if (cnt > (uint32_t)FYB_CAP) {          // far from uniform: the gated direct path takes over
         if (threadIdx.x == 0) atomicOr(flag, 1u);
@@ -481,8 +411,8 @@ hipError_t fy_ranges_init(FyRanges &r, uint32_t n) {
         while (b + 1 < (size_t)nb && x[b + 1] <= j) b++;
         cb[k] = (uint32_t)b;
     }
-    // H [nb][FYB_BLOCKS] lives in the perm buffer; the tables must fit in LDS
-    if ((size_t)nb * FYB_BLOCKS > n || fyb_lds(nb, (int)cb.size()) > FYB_LDS_MAX) return hipSuccess;
+    // the tables must fit in LDS
+    if (fyb_lds(nb, (int)cb.size()) > FYB_LDS_MAX) return hipSuccess;
     hipError_t e = hipMalloc((void **)&r.x, sizeof(uint32_t) * x.size());
     if (e == hipSuccess) e = hipMalloc((void **)&r.cb, sizeof(uint32_t) * cb.size());
     // k_fyb_bucket's range slices, counts and overflow flag (zero: the invariant between
@@ -510,7 +440,7 @@ void fy_ranges_free(FyRanges &r) {
     r.nb = r.ncb = 0;
 }
 
-// scratch: 4n u32 (counts/pairs, buckets/pairs, succ, fw); scan: n/8192 + 2 u32; perm: n u32
+// scratch: 4n u32 (counts, buckets, succ, fw); scan: n/8192 + 2 u32; perm: n u32
 hipError_t fisher_yates_device(const uint32_t *d_J, uint32_t n, uint32_t *scratch, uint32_t *scan, uint32_t *perm,
                                hipStream_t st, const FyRanges *rg, uint32_t *inv) {
     if (n == 0) return hipSuccess;
@@ -523,21 +453,10 @@ hipError_t fisher_yates_device(const uint32_t *d_J, uint32_t n, uint32_t *scratc
         uint32_t *flag = rg->flag;
         const uint32_t chunk = (n + FYB_BLOCKS - 1) / FYB_BLOCKS;
         const size_t lds = fyb_lds(t.nb, t.ncb);
-        static const bool fused = !(getenv("BPPO_FY_FUSED") && atoi(getenv("BPPO_FY_FUSED")) == 0);
-        if (fused) {
-            hipLaunchKernelGGL(k_fyb_bucket, dim3(FYB_BLOCKS), dim3(FYB_THREADS), lds, st, d_J, n, chunk, t,
-                               rg->cursor, rg->P, flag);
-            hipLaunchKernelGGL(k_fyb_link, dim3(t.nb), dim3(FYB_LINK_THREADS), 0, st, n, t, (const uint32_t *)nullptr,
-                               FYB_BLOCKS, (const uint2 *)rg->P, succ, fw, flag, rg->cursor);
-        } else {      // r05's passes (A/B): histogram, scan of the [range][block] counts, scatter
-            uint32_t *H = perm;
-            hipLaunchKernelGGL(k_fyb_hist, dim3(FYB_BLOCKS), dim3(FYB_THREADS), lds, st, d_J, n, chunk, t, H, flag);
-            launch_scan(H, (uint32_t)t.nb * FYB_BLOCKS, scan, H, nullptr, st);
-            hipLaunchKernelGGL(k_fyb_scatter, dim3(FYB_BLOCKS), dim3(FYB_THREADS), lds, st, d_J, n, chunk, t,
-                               (const uint32_t *)H, reinterpret_cast<uint2 *>(scratch));
-            hipLaunchKernelGGL(k_fyb_link, dim3(t.nb), dim3(FYB_LINK_THREADS), 0, st, n, t, (const uint32_t *)H,
-                               FYB_BLOCKS, reinterpret_cast<const uint2 *>(scratch), succ, fw, flag, (uint32_t *)nullptr);
-        }
+        hipLaunchKernelGGL(k_fyb_bucket, dim3(FYB_BLOCKS), dim3(FYB_THREADS), lds, st, d_J, n, chunk, t, rg->cursor,
+                           rg->P, flag);
+        hipLaunchKernelGGL(k_fyb_link, dim3(t.nb), dim3(FYB_LINK_THREADS), 0, st, t, (const uint2 *)rg->P, succ, fw,
+                           flag, rg->cursor);
         // pass 4 (k_fy_final) runs unless a range overflowed; then the one-block
         // direct pass computes the permutation instead
         hipLaunchKernelGGL(k_fy_final, dim3(grid), dim3(256), 0, st, d_J, n, (const uint32_t *)succ,
@@ -546,11 +465,11 @@ hipError_t fisher_yates_device(const uint32_t *d_J, uint32_t n, uint32_t *scratc
         return hipGetLastError();
     }
     // direct path
-    hipLaunchKernelGGL(k_fy_zero, dim3(grid), dim3(256), 0, st, cnt, n, nullptr);
-    hipLaunchKernelGGL(k_fy_count, dim3(grid), dim3(256), 0, st, d_J, n, cnt, nullptr);
-    launch_scan(cnt, n, scan, off, nullptr, st);
-    hipLaunchKernelGGL(k_fy_scatter, dim3(grid), dim3(256), 0, st, d_J, n, (const uint32_t *)off, cnt, bucket, nullptr);
-    hipLaunchKernelGGL(k_fy_link, dim3(grid), dim3(256), 0, st, n, (const uint32_t *)off, bucket, succ, fw, nullptr);
+    hipLaunchKernelGGL(k_fy_zero, dim3(grid), dim3(256), 0, st, cnt, n);
+    hipLaunchKernelGGL(k_fy_count, dim3(grid), dim3(256), 0, st, d_J, n, cnt);
+    launch_scan(cnt, n, scan, off, st);
+    hipLaunchKernelGGL(k_fy_scatter, dim3(grid), dim3(256), 0, st, d_J, n, (const uint32_t *)off, cnt, bucket);
+    hipLaunchKernelGGL(k_fy_link, dim3(grid), dim3(256), 0, st, n, (const uint32_t *)off, bucket, succ, fw);
     hipLaunchKernelGGL(k_fy_final, dim3(grid), dim3(256), 0, st, d_J, n, succ, fw, perm, nullptr, inv);
     return hipGetLastError();
 }

@@ -1854,8 +1854,8 @@ bppo_status launch_minibatch(bppo_ctx *c, uint32_t start, uint32_t n, float ent_
         // (BPPO_MB_EXACT_ALL=1: the exact kernel for every minibatch; BPPO_MB_FIRST_MFMA=1:
         // k_minibatch_mfma for the first, as r05 -- A/B runs)
         // (bppo_set_minibatch_kernel: 1 = exact for every minibatch, 2 = split for every one)
-        static const bool exact_all = getenv("BPPO_MB_EXACT_ALL") != nullptr;
-        static const bool first_mfma = getenv("BPPO_MB_FIRST_MFMA") && atoi(getenv("BPPO_MB_FIRST_MFMA")) == 1;
+        static const bool exact_all = env_set("BPPO_MB_EXACT_ALL");
+        static const bool first_mfma = env_int("BPPO_MB_FIRST_MFMA", 0) == 1;
         const bool use_exact = c->mb_kernel == 1 || (c->mb_kernel == 0 && (exact_all || (exact && first_mfma)));
         const bool exact_fwd = !use_exact && c->mb_kernel == 0 && exact;
         const size_t lds_rows = (size_t)mmf::WAVES * (c->net.n_params + NUM_M) * sizeof(float);
@@ -1864,7 +1864,7 @@ bppo_status launch_minibatch(bppo_ctx *c, uint32_t start, uint32_t n, float ent_
         // HIP timer events around the launch (bench.py's roofline): every launch by default;
         // BPPO_MB_EVENTS=k times every k-th launch of an update (0: none), for A/B runs of the
         // timestamp markers' cost on the stream
-        static const int ev_every = getenv("BPPO_MB_EVENTS") ? atoi(getenv("BPPO_MB_EVENTS")) : 1;
+        static const int ev_every = env_int("BPPO_MB_EVENTS", 1);
         const bool timed = ev_every > 0 && c->mb_launch++ % ev_every == 0;
         const int ei = timed && c->mb_ev_n < bppo_ctx::MB_EV ? c->mb_ev_n++ : -1;
         // (the roofline's "exact" share: the update's first minibatch, whichever kernel runs it)
@@ -1877,7 +1877,7 @@ bppo_status launch_minibatch(bppo_ctx *c, uint32_t start, uint32_t n, float ent_
             hipLaunchKernelGGL(k_minibatch_split<false>, dim3(blocks), dim3(64 * mmf::WAVES), lds_split, c->stream, g);
         if (ei >= 0) BPPO_HIP(c, hipEventRecord(c->mb_ev[ei][1], c->stream));
 #ifdef BPPO_MB_STAMPS
-        if ((!use_exact && !exact_fwd) || getenv("BPPO_MB_STAMPS_EXACT")) {
+        if ((!use_exact && !exact_fwd) || env_set("BPPO_MB_STAMPS_EXACT")) {
             // mean per-wave cycles per segment of the split launches (the exact kernel's with
             // BPPO_MB_STAMPS_EXACT), accumulated over launches; printed every 16
             static double acc_s[MB_NSEG] = {};
@@ -1954,14 +1954,10 @@ bppo_status launch_adam(bppo_ctx *c, float lr, const float *c1, const float *c2,
 // caller has waited for the stream
 bppo_status launch_explained_variance(bppo_ctx *c, const float *valid) {
     const size_t n = (size_t)c->T * c->N;
-    // BPPO_ZERO_COPY=1: the block sums straight into the pinned buffer (its device address)
-    const bool zc = zero_copy();
-    hipLaunchKernelGGL(k_ev, dim3(STAT_BLOCKS), dim3(256), 0, c->stream, n, c->d_val, c->d_ret, valid,
-                       zc ? c->hd_red : c->d_red);
+    hipLaunchKernelGGL(k_ev, dim3(STAT_BLOCKS), dim3(256), 0, c->stream, n, c->d_val, c->d_ret, valid, c->d_red);
     TRY(launch_check(c, __func__));
-    if (!zc)
-        BPPO_HIP(c, hipMemcpyAsync(c->h_red, c->d_red, sizeof(double) * 4 * STAT_BLOCKS,
-                                   hipMemcpyDeviceToHost, c->stream));
+    BPPO_HIP(c, hipMemcpyAsync(c->h_red, c->d_red, sizeof(double) * 4 * STAT_BLOCKS, hipMemcpyDeviceToHost,
+                               c->stream));
     return BPPO_OK;
 }
 void explained_variance_sums(bppo_ctx *c, double *out4) {

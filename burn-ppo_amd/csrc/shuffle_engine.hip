@@ -48,7 +48,7 @@ namespace bppo {
 
 static bool shuf_debug() {
     static int v = -1;
-    if (v < 0) v = getenv("BPPO_SHUFFLE_DEBUG") ? 1 : 0;
+    if (v < 0) v = env_set("BPPO_SHUFFLE_DEBUG") ? 1 : 0;
     return v == 1;
 }
 static double shuf_t_ms() {   // debug timestamps: ms since the first call
@@ -194,15 +194,6 @@ __global__ void __launch_bounds__(64 * XJ_WAVES) k_expand_J(Key8 key, uint64_t s
     }
 }
 
-// A job's J expansions on the copy stream wait for the end of the update the caller enqueued
-// last (its ev_upd) when BPPO_XJ_GATE is set: 1 every epoch, 2 epochs after the first.  No
-// deadlock: an update waits only for its own job's epochs, and the caller records its ev_upd
-// after enqueuing every epoch it runs, i.e. after those expansions were launched
-void ShuffleEngine::xj_gate_wait(int e) {
-    static const int mode = getenv("BPPO_XJ_GATE") ? atoi(getenv("BPPO_XJ_GATE")) : 0;
-    if (gate && (mode == 1 || (mode == 2 && e > 0))) hip_note(hipStreamWaitEvent(copy, gate, 0), "hipStreamWaitEvent");
-}
-
 // expected words per shuffle of n and its std dev: draw with range R accepts with
 // probability a = (R << lz(R)) / 2^32 (uniform.rs zone), geometric word count
 static void shuffle_word_stats(uint32_t n, double &mean, double &sd) {
@@ -249,10 +240,10 @@ bppo_status ShuffleEngine::init(int device, const Key8 &k, uint64_t strm, uint32
     // BPPO_HOST_THREADS: this rank's CPU budget (bench.py: the CPUs this process may
     // use / ranks on the node), so 8 ranks of one node do not oversubscribe it.
     // K and the word producers scale with it; 16 CPUs (one GPU's share) -> K = 6.
-    host_cpus = 16;
-    if (const char *e = getenv("BPPO_HOST_THREADS")) host_cpus = std::max(1, atoi(e));
+    host_cpus = std::max(1, env_int("BPPO_HOST_THREADS", 16));
     K = std::max(1, std::min(6, (6 * host_cpus + 8) / 16));
-    if (const char *e = getenv("BPPO_SHUFFLE_SPEC")) K = std::max(0, atoi(e));
+    const bool spec_set = env_set("BPPO_SHUFFLE_SPEC");
+    if (spec_set) K = std::max(0, env_int("BPPO_SHUFFLE_SPEC", 0));
     // C leading epochs of the next job are speculated during this job (their walks
     // get a whole job of head start; later epochs' walks start with their job)
     C = std::min(2, std::max(epochs, 1));
@@ -267,14 +258,14 @@ bppo_status ShuffleEngine::init(int device, const Key8 &k, uint64_t strm, uint32
     // depth 2 gives the walks of e+3 that head start.  A/B on two boxes, 3 + 2 runs each:
     // 12.41-12.57 vs 12.42-13.75 ms/update, shuffle_wait ~0 vs 0.7-5 ms,
     // profiles/r04_windows/frontier_ab.txt); depth 1 below 8 CPUs (more CPU per update)
-    fr_depth = getenv("BPPO_SHUFFLE_FRONTIER") ? atoi(getenv("BPPO_SHUFFLE_FRONTIER")) : (host_cpus >= 8 ? 2 : 1);
+    fr_depth = env_int("BPPO_SHUFFLE_FRONTIER", host_cpus >= 8 ? 2 : 1);
     if (fr_depth > 0 && epochs >= 3 && K > 0) {
         C = std::min(fr_depth + 1, epochs - 1);
         fr_depth = C - 1;
         // one-sigma anchors: K = 5 over +-2 sigma misses ~1 in 40 boundaries and
         // meets after ~2 M words (scripts/microbench/comb_sim.cpp); fewer walks
         // leave the true walk and the met chains their CPUs
-        if (!getenv("BPPO_SHUFFLE_SPEC")) K = std::max(1, std::min(fr_depth >= 2 ? 4 : 5, (5 * host_cpus + 8) / 16));
+        if (!spec_set) K = std::max(1, std::min(fr_depth >= 2 ? 4 : 5, (5 * host_cpus + 8) / 16));
     } else {
         fr_depth = 0;
     }
@@ -284,11 +275,8 @@ bppo_status ShuffleEngine::init(int device, const Key8 &k, uint64_t strm, uint32
     // and the epochs' walks go in pairs, two chains interleaved per thread (half the
     // walking CPU of one chain per thread: the walker is latency-bound)
     // (only when the rank has fewer CPUs than epochs: with one CPU per epoch each walk
-    // runs alone, 0.45 instead of 0.54 ns per word of wall time; BPPO_SHUFFLE_PAIR=0/1 forces)
-    keep_guess = !(getenv("BPPO_SHUFFLE_KEEP_GUESS") && atoi(getenv("BPPO_SHUFFLE_KEEP_GUESS")) == 0);
+    // runs alone, 0.45 instead of 0.54 ns per word of wall time)
     pair = win && host_cpus < epochs;
-    if (const char *e = getenv("BPPO_SHUFFLE_PAIR")) pair = win && atoi(e) != 0;
-    win_producers = win && getenv("BPPO_SHUFFLE_WIN_PRODUCERS") && atoi(getenv("BPPO_SHUFFLE_WIN_PRODUCERS")) == 1;
     // opt-in (BPPO_SHUFFLE_GPU_WORDS=1): the job's words, made on the GPU for the J
     // expansion a whole job ahead, are copied (hipMemcpyAsync D2H) to the walks' pinned
     // host buffer, so the walks make no words themselves: 2-CPU walk 14.0 -> 8.3 ms and
@@ -298,8 +286,7 @@ bppo_status ShuffleEngine::init(int device, const Key8 &k, uint64_t strm, uint32
     // SDMA path (hsa_amd_memory_async_copy, r03n: 10-50 GB/s by box) is the way to keep
     // the CPU saving without the CU cost.  (r04k's first form, kernels writing host memory
     // over PCIe, stretched the rollout 1.2 -> 4.0 ms.)
-    win_gpu_words = win && !win_producers && getenv("BPPO_SHUFFLE_GPU_WORDS") &&
-                    atoi(getenv("BPPO_SHUFFLE_GPU_WORDS")) == 1;
+    win_gpu_words = win && env_int("BPPO_SHUFFLE_GPU_WORDS", 0) == 1;
     // exact continuations need the last epoch in the in-job groups
     const bool cont_on = !win && epochs - 1 >= C;
     K = std::min(K, SHUF_MAX_SPEC / (std::max(epochs - C, 0) + 2 * C + (cont_on ? 2 : 0)));
@@ -330,7 +317,7 @@ bppo_status ShuffleEngine::init(int device, const Key8 &k, uint64_t strm, uint32
             err = "shuffle events: creation failed";
             return BPPO_ERR_HIP;
         }
-    if (win && getenv("BPPO_SHUFFLE_GPU_WORDS") && atoi(getenv("BPPO_SHUFFLE_GPU_WORDS")) == 1 &&
+    if (win_gpu_words &&
         (hipStreamCreateWithFlags(&d2h, hipStreamNonBlocking) != hipSuccess ||
          hipEventCreateWithFlags(&words_made, hipEventDisableTiming) != hipSuccess)) {
         err = "shuffle word copies: stream creation failed";
@@ -384,7 +371,7 @@ bppo_status ShuffleEngine::init(int device, const Key8 &k, uint64_t strm, uint32
     const uint64_t nck = (uint64_t)((Ew + 24.0 * sigma) / SHUF_CK) + 4;
     for (int i = 0; i < nspec; i++) spec[i].ck.assign(nck, 0xFFFFFFFFu);
     for (int i = 0; i < nspec; i++) workers.emplace_back([this, i]() { worker(i); });
-    const int ngen = win && !win_producers ? 0 : std::max(1, std::min(4, host_cpus / 4));
+    const int ngen = win ? 0 : std::max(1, std::min(4, host_cpus / 4));   // windowed: the walks make their words
     for (int i = 0; i < ngen; i++) gens.emplace_back([this]() { generator(); });
     th = std::thread([this]() { run(); });
     return BPPO_OK;
@@ -822,8 +809,7 @@ void ShuffleEngine::run() {
             const WordBuf &Pv = wb[b ^ 1];
             alt_b = -1;
             uint64_t base0 = s0;
-            static const bool reuse = !(getenv("BPPO_SHUFFLE_CARRY_REUSE") && atoi(getenv("BPPO_SHUFFLE_CARRY_REUSE")) == 0);
-            if (reuse && seq > 1 && Pv.nreg == 2 && Pv.reg[1].len > 0 && Pv.reg[1].base <= s0 &&
+            if (seq > 1 && Pv.nreg == 2 && Pv.reg[1].len > 0 && Pv.reg[1].base <= s0 &&
                 Pv.reg[1].base + Pv.reg[1].len > s0 && Pv.reg[1].base + Pv.reg[1].len < end0) {
                 alt_b = b ^ 1;
                 alt_reg = Pv.reg[1];
@@ -961,7 +947,7 @@ void ShuffleEngine::run() {
                 for (int i = met; i >= 0; i = spec[i].merged_to.load(std::memory_order_acquire)) keep[i] = true;
                 for (int g = 0; g < 2; g++)
                     for (int i = g ? s0 : c0; i < (g ? s1 : c1); i++)
-                        if (!keep[i] && !(on_cont && g == 1 && keep_guess))
+                        if (!keep[i] && !(on_cont && g == 1))
                             spec[i].stop.store(true, std::memory_order_relaxed);
                 return true;
             };
@@ -973,7 +959,7 @@ void ShuffleEngine::run() {
                     const bool chain_done = spec[f].done.load(std::memory_order_acquire) != 0 &&
                                             spec[f].merged_to.load(std::memory_order_acquire) < 0;
                     uint32_t rr = 0;
-                    const bool recheck = keep_guess && s1 > s0 && met >= c0 && met < c1;
+                    const bool recheck = s1 > s0 && met >= c0 && met < c1;
                     for (uint64_t q = (pos / SHUF_CK + 1) * SHUF_CK; r >= 2 && peek(met, q, &rr) == 1; q += SHUF_CK) {
                         tck.push_back({q, rr});
                         pos = q;
@@ -1052,12 +1038,10 @@ void ShuffleEngine::run() {
                     // guessed walks started when the boundary fr_depth epochs earlier
                     // resolved, so the two nearest x may be far ahead on the same chain
                     // once they coalesce with it: keep them beside the continuation (the
-                    // true walk follows whichever is ahead).  keep_guess = 0: r02's rule
-                    // (an exact continuation stops every guessed walk).
+                    // true walk follows whichever is ahead).
                     const uint64_t x = pos + gap;
-                    const int ex = cont0 ? prune(ccn0, ccn0 + K, x) : -1;
-                    if (ex >= 0 && !keep_guess) for (int i = cn0; i < cn0 + K; i++) spec[i].stop.store(true, std::memory_order_relaxed);
-                    else prune(cn0, cn0 + K, x);
+                    if (cont0) prune(ccn0, ccn0 + K, x);
+                    prune(cn0, cn0 + K, x);
                 }
             }
             // frontier: the boundary fr_depth epochs past this one now has an exact
@@ -1092,7 +1076,6 @@ void ShuffleEngine::run() {
                     }
                 Seg *dS = d_seg[slot] + (size_t)e * maxseg;
                 hip_note(hipMemcpyAsync(dS, S, sizeof(Seg) * (size_t)std::max(ns, 1), hipMemcpyHostToDevice, copy), "hipMemcpyAsync");
-                xj_gate_wait(e);
                 hipLaunchKernelGGL(k_expand_J, dim3((unsigned)((std::max(ns, 1) + XJ_WAVES - 1) / XJ_WAVES)),
                                    dim3(64 * XJ_WAVES), 0, copy, key, stream, (const Seg *)dS, ns, wr,
                                    d_J[slot] + (size_t)e * n);
@@ -1191,20 +1174,10 @@ bool ShuffleEngine::run_windowed(int slot, uint64_t start) {
     // this job's fixed span plus the next rollout's words)
     if (W.gpu) make_words(wb[b ^ 1], start + (uint64_t)epochs * win + gap, next_order);
     {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return gen_active == 0 || quit; });
-        gen_order.clear();
         // every word of a windowed job is on a true chain and read by exactly one walk:
-        // the walks make their own pieces (no producer threads making the same words
-        // twice when the walks outrun them; BPPO_SHUFFLE_WIN_PRODUCERS=1 restores them)
-        if (win_producers)
-            for (size_t c : order) {
-                const WordBuf::Region &R = W.reg[c * SHUF_CHUNK / rlen];
-                gen_order.push_back({R.base + (c * SHUF_CHUNK - R.off), c});
-            }
-        gen_buf = &W;
-        gen_next.store(0, std::memory_order_relaxed);
-        gen_job++;
+        // the walks make their own pieces (a windowed engine has no producer threads, which
+        // made the same words twice when the walks outran them)
+        std::lock_guard<std::mutex> lk(mu);
         for (int e = 0; e < epochs; e++) launch_walk(e, start + (uint64_t)e * win, b);
     }
     cv.notify_all();
@@ -1244,7 +1217,6 @@ bool ShuffleEngine::run_windowed(int slot, uint64_t start) {
             wr.ptr[0] = W.d + W.reg[e].off; wr.base[0] = W.reg[e].base; wr.len[0] = W.reg[e].len; wr.n = 1;
             Seg *dS = d_seg[slot] + (size_t)e * maxseg;
             hip_note(hipMemcpyAsync(dS, S, sizeof(Seg) * (size_t)std::max(ns, 1), hipMemcpyHostToDevice, copy), "hipMemcpyAsync");
-            xj_gate_wait(e);
             hipLaunchKernelGGL(k_expand_J, dim3((unsigned)((std::max(ns, 1) + XJ_WAVES - 1) / XJ_WAVES)),
                                dim3(64 * XJ_WAVES), 0, copy, key, stream, (const Seg *)dS, ns, wr,
                                d_J[slot] + (size_t)e * n);
@@ -1299,14 +1271,11 @@ void ShuffleEngine::shutdown() {
     }
 }
 
-// side streams (J expansion, Fisher-Yates): lowest priority; BPPO_SIDE_PRIO=normal (A/B)
-// creates them at the default priority
+// side streams (J expansion, Fisher-Yates): lowest priority
 hipError_t make_side_stream(int device, hipStream_t *st) {
     (void)device;
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    static const bool normal = getenv("BPPO_SIDE_PRIO") && std::string(getenv("BPPO_SIDE_PRIO")) == "normal";
-    if (normal) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
     return hipStreamCreateWithPriority(st, hipStreamNonBlocking, lo);
 }
 

@@ -283,7 +283,7 @@ bppo_status wide_minibatch(bppo_ctx *c, uint32_t start, uint32_t mb, double ent_
     // -- are amplified by Adam over many tiny minibatches (a 72-row Liar's Dice CTDE update
     // drifts 1e-3 from the oracle by minibatch 3 with the split, 0 with the exact chains:
     // profiles/r05c/popart_split_probe.log)
-    static const bool exact_all = getenv("BPPO_MB_EXACT_ALL") != nullptr;
+    static const bool exact_all = env_set("BPPO_MB_EXACT_ALL");
     const bool big = rows >= WIDE_SPLIT_MIN_ROWS;
     const int split = n.n_conv == 0 && (c->mb_kernel == 2 || (c->mb_kernel == 0 && !first && !exact_all && big)) ? 1 : 0;
     // the backward (input and weight gradients) needs f32 accuracy only -- the ratio is
