@@ -54,6 +54,17 @@ class RolloutInfo(C.Structure):
                 ("pad", C.c_int32), ("rng_word_pos", C.c_uint64)]
 
 
+class EvalConfig(C.Structure):
+    _fields_ = [("num_games", C.c_int32), ("max_steps", C.c_int32), ("seed", C.c_uint64),
+                ("temp_initial", C.c_float), ("temp_final", C.c_float), ("temp_cutoff", C.c_int32),
+                ("temp_decay", C.c_int32)]
+
+
+class EvalGame(C.Structure):
+    _fields_ = [("total_reward", C.c_float * MAX_PLAYERS), ("placement", C.c_int32 * MAX_PLAYERS),
+                ("length", C.c_int32), ("env_index", C.c_int32), ("perm_index", C.c_int32), ("step", C.c_int32)]
+
+
 METRIC_NAMES = ("policy_loss", "value_loss", "entropy", "entropy_scaled", "approx_kl", "clip_fraction",
                 "explained_variance", "total_loss", "value_mean", "returns_mean", "adv_mean_raw",
                 "adv_std_raw", "adv_min_raw", "adv_max_raw", "value_error_mean", "value_error_std",
@@ -87,11 +98,14 @@ EXPORTS = (
     "bppo_config_size", "bppo_update_metrics_size", "bppo_episode_size", "bppo_rollout_info_size",
     "bppo_set_explained_variance_mode", "bppo_set_minibatch_kernel", "bppo_set_rank",
     "bppo_debug_record_params",
+    "bppo_evaluate", "bppo_eval_config_size", "bppo_eval_game_size", "bppo_debug_eval_sample",
+    "bppo_debug_eval_perms",
 )
 
 # ABI struct -> the library's sizeof export (checked when the library loads)
 STRUCT_SIZES = {"bppo_config_size": Config, "bppo_update_metrics_size": UpdateMetrics,
-                "bppo_episode_size": Episode, "bppo_rollout_info_size": RolloutInfo}
+                "bppo_episode_size": Episode, "bppo_rollout_info_size": RolloutInfo,
+                "bppo_eval_config_size": EvalConfig, "bppo_eval_game_size": EvalGame}
 
 _lib = None
 
@@ -173,6 +187,10 @@ def lib():
         "bppo_set_explained_variance_mode": (i32, [vp, i32]),
         "bppo_set_minibatch_kernel": (i32, [vp, i32]),
         "bppo_debug_record_params": (i32, [vp, vp, i32]),
+        "bppo_evaluate": (i32, [vp, C.POINTER(EvalConfig), i32, vp, vp, vp, vp, vp, vp, i32, vp, i32,
+                                C.POINTER(i32), C.POINTER(u64)]),
+        "bppo_debug_eval_sample": (i32, [i32, i32, i32, vp, vp, vp, u64, u64, u64, vp, vp]),
+        "bppo_debug_eval_perms": (i32, [i32, vp]),
     }
     for name in STRUCT_SIZES:
         sig[name] = (sz, [])

@@ -1,0 +1,206 @@
+"""Stats-mode evaluation (eval.rs): play N games between checkpoints on the device.
+
+    TempSchedule            eval.rs:76-216  (get_temp, env defaults, argument errors)
+    generate_permutations   eval.rs:1591-1612 (Heap's algorithm, as written)
+    rewards_to_placements   eval.rs:276-306
+    evaluate                eval.rs:1621-1877 run_stats_mode_env -> EvalStats (eval.rs:315-390)
+
+The games run inside libbppo (bppo_evaluate, csrc/eval.hip) on a context of their
+own.  Checkpoint loading stays with bppo.checkpoint; ratings and printing are not
+part of this module."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .ppo import Context
+
+# E::EVAL_TEMP and E::EVAL_TEMP_CUTOFF (connect_four.rs:219-221, liars_dice.rs:454,
+# skull.rs:1052; the trait's defaults are 0.3 and None, env.rs:53-58)
+EVAL_TEMP = {"connect_four": 0.4, "liars_dice": 1.0, "skull": 1.0}
+EVAL_TEMP_CUTOFF = {"connect_four": (10, 0.0), "liars_dice": None, "skull": None}
+
+
+_libm = None
+
+
+def _fmaf(a, b, c):
+    """f32 fused multiply-add (Rust's f32::mul_add) from the platform libm: one rounding"""
+    global _libm
+    if _libm is None:
+        import ctypes.util
+        _libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+        _libm.fmaf.restype = C.c_float
+        _libm.fmaf.argtypes = [C.c_float, C.c_float, C.c_float]
+    return _libm.fmaf(float(a), float(b), float(c))
+
+
+class TempSchedule:
+    """eval.rs:76-91: initial, final_temp, cutoff (None = constant), decay."""
+
+    def __init__(self, initial, final_temp=0.0, cutoff=None, decay=False):
+        self.initial = np.float32(initial)
+        self.final_temp = np.float32(final_temp)
+        self.cutoff = None if cutoff is None else int(cutoff)
+        self.decay = bool(decay)
+
+    @classmethod
+    def from_args(cls, env, temp=None, temp_final=None, temp_cutoff=None, no_temp_cutoff=False,
+                  temp_decay=False):
+        """from_args_with_env_defaults (eval.rs:99-141): the env's EVAL_TEMP / EVAL_TEMP_CUTOFF
+        unless overridden; temp_final or temp_decay without any cutoff is an error."""
+        default = EVAL_TEMP.get(env, 0.3)
+        env_cutoff = EVAL_TEMP_CUTOFF.get(env)
+        if no_temp_cutoff:
+            return cls(default if temp is None else temp, 0.0, None, False)
+        cutoff = temp_cutoff if temp_cutoff is not None else (env_cutoff[0] if env_cutoff else None)
+        if cutoff is None:
+            if temp_final is not None:
+                raise ValueError("--temp-final requires --temp-cutoff to be set (or env default)")
+            if temp_decay:
+                raise ValueError("--temp-decay requires --temp-cutoff to be set (or env default)")
+        final = temp_final if temp_final is not None else (env_cutoff[1] if env_cutoff else 0.0)
+        return cls(default if temp is None else temp, final, cutoff, temp_decay)
+
+    @classmethod
+    def env_default(cls, env):
+        return cls.from_args(env)
+
+    def get_temp(self, move_num):
+        """eval.rs:200-216 in f32: the decay is one fused multiply-add."""
+        if self.cutoff is None:
+            return self.initial
+        if move_num >= self.cutoff:
+            return self.final_temp
+        if not self.decay:
+            return self.initial
+        t = np.float32(move_num) / np.float32(self.cutoff)
+        return np.float32(_fmaf(t, self.final_temp - self.initial, self.initial))
+
+
+def generate_permutations(n):
+    """eval.rs:1591-1612: all permutations of 0..n by Heap's algorithm, in its order."""
+    out, arr = [], list(range(n))
+
+    def heap_permute(k):
+        if k == 1:
+            out.append(list(arr))
+            return
+        heap_permute(k - 1)
+        for i in range(k - 1):
+            j = i if k % 2 == 0 else 0
+            arr[j], arr[k - 1] = arr[k - 1], arr[j]
+            heap_permute(k - 1)
+
+    heap_permute(n)
+    return out
+
+
+def rewards_to_placements(rewards):
+    """eval.rs:276-306: 1 = first; rewards within 1e-6 of a tie group's first share its place."""
+    r = [np.float32(x) for x in rewards]
+    order = sorted(range(len(r)), key=lambda i: -r[i])      # stable, descending
+    pl = [0] * len(r)
+    cur, i = 1, 0
+    while i < len(order):
+        first = r[order[i]]
+        tied = 0
+        while i + tied < len(order) and abs(np.float32(r[order[i + tied]] - first)) < np.float32(1e-6):
+            tied += 1
+        for j in range(tied):
+            pl[order[i + j]] = cur
+        cur += tied
+        i += tied
+    return pl
+
+
+class EvalStats:
+    """eval.rs:315-390: placement counts per checkpoint, the game list, episode lengths."""
+
+    def __init__(self, num_players):
+        self.num_players = num_players
+        self.placements = np.zeros((num_players, num_players), np.int64)
+        self.total_games = 0
+        self.game_rewards = []
+        self.episode_lengths = []
+        self.game_outcomes = []
+        self.games = []          # (env_index, perm_index, step) of each recorded game
+        self.rng_word_pos = 0
+
+    def record_with_rewards(self, outcome, rewards, length):
+        self.game_rewards.append([float(x) for x in rewards])
+        self.episode_lengths.append(int(length))
+        self.record(outcome)
+
+    def record(self, outcome):
+        self.total_games += 1
+        self.game_outcomes.append(list(outcome))
+        for i, place in enumerate(outcome):
+            if 0 < place <= self.num_players:
+                self.placements[i][place - 1] += 1
+
+    def wins(self, player):
+        return sum(1 for o in self.game_outcomes if o[player] == 1 and sum(p == 1 for p in o) == 1)
+
+    def losses(self, player):
+        return sum(1 for o in self.game_outcomes if o[player] == self.num_players)
+
+    def draws(self):
+        return sum(1 for o in self.game_outcomes if all(p == 1 for p in o))
+
+
+def evaluate_ctx(ctx, models, normalizers, seat_model, num_games, temp_schedule, seed, max_steps=None):
+    """bppo_evaluate on an existing context (its VecEnv is reset and overwritten).
+    models[k]: a flat parameter vector, or None for the random player; normalizers[k]:
+    (mean, m2, count) or None.  -> (games as a numpy record array, rng word position)"""
+    K, D = len(models), ctx.obs_dim
+    params = np.zeros((K, ctx.n_params), np.float32)
+    is_random = np.zeros(K, np.int32)
+    mean = np.zeros((K, D)); m2 = np.zeros((K, D)); cnt = np.zeros(K)
+    for k, m in enumerate(models):
+        if m is None:
+            is_random[k] = 1
+        else:
+            params[k] = np.asarray(m, np.float32).reshape(-1)
+        nm = normalizers[k] if normalizers else None
+        if nm is not None:
+            mean[k], m2[k], cnt[k] = nm
+    seats = np.ascontiguousarray(seat_model, np.int32)
+    if max_steps is None:
+        # every env plays at most ceil(num_games / num_envs) + 1 games; no game of these envs
+        # runs longer than a few hundred moves
+        max_steps = 1000 * (num_games // max(ctx.N, 1) + 2)
+    cfg = L.EvalConfig(num_games=int(num_games), max_steps=int(max_steps), seed=int(seed),
+                       temp_initial=float(temp_schedule.initial), temp_final=float(temp_schedule.final_temp),
+                       temp_cutoff=-1 if temp_schedule.cutoff is None else int(temp_schedule.cutoff),
+                       temp_decay=int(temp_schedule.decay))
+    games = (L.EvalGame * max(int(num_games), 1))()
+    n = C.c_int32()
+    pos = C.c_uint64()
+    st = L.lib().bppo_evaluate(ctx.h, C.byref(cfg), K, params.ctypes.data, mean.ctypes.data, m2.ctypes.data,
+                               cnt.ctypes.data, is_random.ctypes.data, seats.ctypes.data, len(seats),
+                               C.cast(games, C.c_void_p), int(num_games), C.byref(n), C.byref(pos))
+    L.check(st, ctx.h)
+    rec = np.frombuffer(games, dtype=np.dtype(L.EvalGame), count=max(int(num_games), 1)).copy()
+    return rec[:min(n.value, int(num_games))], pos.value
+
+
+def evaluate(config, models, normalizers, seat_model, num_games, temp_schedule=None, seed=0, device=0,
+             max_steps=None):
+    """run_stats_mode_env (eval.rs:1621-1877) with config["num_envs"] parallel games on a
+    context of its own: models[seat_model[c]] plays checkpoint c (None = the random
+    player), every permutation of the seats in turn.  -> EvalStats"""
+    if temp_schedule is None:
+        temp_schedule = TempSchedule.env_default(config["env"])
+    ctx = Context(config, device=device)
+    try:
+        rec, pos = evaluate_ctx(ctx, models, normalizers, seat_model, num_games, temp_schedule, seed, max_steps)
+        ncp = len(seat_model)
+    finally:
+        ctx.close()
+    stats = EvalStats(ncp)
+    for g in rec:
+        stats.record_with_rewards([int(x) for x in g["placement"][:ncp]], g["total_reward"][:ncp], g["length"])
+        stats.games.append((int(g["env_index"]), int(g["perm_index"]), int(g["step"])))
+    stats.rng_word_pos = pos
+    return stats

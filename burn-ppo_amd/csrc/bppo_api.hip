@@ -429,7 +429,7 @@ extern "C" size_t bppo_num_params(const bppo_ctx *c) { return c ? c->net.n_param
 // a rollout bppo_train_steps enqueued ahead (and left pending by an error) was drawn
 // with the state these setters replace: drop it (the envs and the RNG stay where it
 // left them; the next bppo_collect_rollouts draws a new one)
-static void drop_prefetch(bppo_ctx *c) {
+void drop_prefetch(bppo_ctx *c) {   // (also eval.hip)
     if (!c->prefetched) return;
     c->prefetched = false;
     c->collected = 0;

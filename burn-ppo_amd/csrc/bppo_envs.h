@@ -641,4 +641,53 @@ __device__ __forceinline__ void sk_priv(const SKState &s, float *g) {
     }
 }
 
+// ========================================================== game_outcome ==
+// Environment::game_outcome of a finished game, read before the auto-reset
+// (env.rs:442-450): placements per seat (1 = first), seats past the game's
+// players 0.  Returns false for the reference's None (the game ended without
+// game_over, e.g. on an invalid action), where the caller ranks the rewards.
+
+// connect_four.rs:301-310.  The state keeps no winner: a win leaves `cur` on the
+// winner (c4_step does not switch it), and a full board without a win leaves it
+// on the last mover, who then has no line of four.
+__device__ __forceinline__ bool c4_has_four(uint64_t m) {
+    const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1};
+    for (int r = 0; r < 6; r++)
+        for (int c = 0; c < 7; c++)
+            for (int d = 0; d < 4; d++) {
+                const int r3 = r + 3 * dr[d], c3 = c + 3 * dc[d];
+                if (r3 >= 6 || c3 < 0 || c3 >= 7) continue;
+                bool all = true;
+                for (int i = 0; i < 4; i++) all = all && ((m >> ((r + i * dr[d]) * 7 + c + i * dc[d])) & 1ull);
+                if (all) return true;
+            }
+    return false;
+}
+__device__ __forceinline__ bool c4_outcome(const C4State &s, int32_t out[6]) {
+    for (int p = 0; p < 6; p++) out[p] = 0;
+    if (!s.over) return false;
+    const int w = c4_has_four(s.p[s.cur - 1]) ? s.cur : 0;
+    out[0] = w == 2 ? 2 : 1;
+    out[1] = w == 1 ? 2 : 1;      // a tie: both first
+    return true;
+}
+
+// liars_dice.rs:586-601: elimination order to placements (first out = last place)
+__device__ __forceinline__ bool ld_outcome(const LDState &s, int32_t out[6]) {
+    for (int p = 0; p < 6; p++) out[p] = 0;
+    if (!s.game_over) return false;
+    for (int o = 0; o < s.num_elim; o++) out[s.elim_order[o]] = LD_P - o;
+    return true;
+}
+
+// skull.rs:1338-1343: compute_placements
+__device__ __forceinline__ bool sk_outcome(const SKState &s, int32_t out[6]) {
+    for (int p = 0; p < 6; p++) out[p] = 0;
+    if (!s.game_over) return false;
+    int pl[SK_P];
+    sk_placements(s, pl);
+    for (int p = 0; p < s.n; p++) out[p] = pl[p];
+    return true;
+}
+
 }  // namespace bppo

@@ -446,6 +446,9 @@ struct bppo_ctx {
     float ev_ref = 0.0f;
 };
 
+// a state setter drops a rollout that bppo_train_steps enqueued ahead (bppo_api.hip)
+void drop_prefetch(bppo_ctx *c);
+
 namespace bppo {
 // runtime switches: every BPPO_* variable is read through these two
 inline bool env_set(const char *name) { return getenv(name) != nullptr; }               // present, any value
@@ -535,6 +538,8 @@ bppo_status opp_step_seats(bppo_ctx *c, int t);
 bppo_status opp_rollout_end(bppo_ctx *c);
 bppo_status opp_compact_valid(bppo_ctx *c);
 bppo_status opp_map_perm(bppo_ctx *c, uint32_t n);
+bppo_status opp_sort_rows(bppo_ctx *c, const int32_t *group, const int32_t *gpos, const float *src, float *dst);
+bppo_status opp_select(bppo_ctx *c, const int32_t *group, const int32_t *gpos, const float *src, float *dst);
 bppo_status wide_collect(bppo_ctx *c, uint64_t base);
 bppo_status wide_bootstrap_gae(bppo_ctx *c);
 bppo_status wide_minibatch(bppo_ctx *c, uint32_t start, uint32_t n, double ent_coef, bool first);

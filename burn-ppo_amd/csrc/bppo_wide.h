@@ -9,6 +9,14 @@ namespace bppo {
 
 struct EpisodeRec;
 
+// a finished game as the evaluation loop (eval.hip) needs it: the episode's totals and
+// Environment::game_outcome, captured before the auto-reset (env.rs:442-450)
+struct EvalOutcome {
+    float total_reward[6];   // per seat
+    int32_t placement[6];    // per seat, 1 = first; valid when has_outcome
+    int32_t length, has_outcome;
+};
+
 struct WideStepArgs {
     int N, t;
     void *state;
@@ -26,6 +34,10 @@ struct WideStepArgs {
     int32_t *ep_count;
     int eps_cap;
     int32_t *err;        // bit 3: an action outside the env's mask (Skull panics, skull.rs:1113-1128)
+    // evaluation only (null on every training call): envs marked terminal are neither stepped
+    // nor reset (env.rs:429-432); a finished game's totals and outcome go to sink[e]
+    const uint8_t *frozen = nullptr;
+    EvalOutcome *sink = nullptr;
 };
 
 struct SampleArgs {
@@ -76,6 +88,8 @@ hipError_t wide_env_reset(int kind, hipStream_t st, int N, uint64_t seed_base, i
 hipError_t wide_env_observe(int kind, int with_priv, hipStream_t st, int N, const void *state, float *xc,
                             uint8_t *mask, int32_t *players);
 hipError_t wide_env_step(int kind, hipStream_t st, const WideStepArgs &a);
+// Environment::reset of every env once more (VecEnv::set_all_num_players, env.rs:313-326)
+hipError_t wide_env_reset_again(int kind, hipStream_t st, int N, uint64_t seed_base, void *state, uint64_t *env_pos);
 hipError_t wide_sample(int A, hipStream_t st, const SampleArgs &g);
 hipError_t wide_boot_lvpp(hipStream_t st, int N, int P, const float *values, const int32_t *players, float *lvpp);
 hipError_t wide_gather(hipStream_t st, const uint32_t *perm, uint32_t start, uint32_t n, const float *src, int L,

@@ -1,0 +1,555 @@
+// eval.hip — stats-mode evaluation on the device: run_stats_mode_env
+// (eval.rs:1621-1877), the engine of `eval --num-games` and of the tournament
+// pods (tournament.rs:1843).  The same machine as the opponent-pool rollout
+// (opponents.hip) with a temperature sampler, envs that can be frozen, game
+// outcomes captured before the auto-reset, and the games cap + freeze rule.
+//
+// Per loop iteration, on the context's stream:
+//   observe          rows, masks, player to move (k_wide_observe)
+//   k_eval_group     each active env's mover model seat_model[perm[player]]
+//                    (eval.rs:1697-1704), its row in the step's model-major order, its
+//                    temperature (eval.rs:1766) and, if it draws, its draw index: models
+//                    in ascending index, within a model the non-frozen envs in ascending
+//                    index (eval.rs:1685-1769)
+//   one host read    {games completed, active envs, group bases}: sizes the per-model
+//                    GEMMs and ends the loop (eval.rs:1670-1674)
+//   per model        rows sorted (k_opp_sort_rows), its obs normalizer
+//                    (eval.rs:1727-1734), wide_forward_actor, logits selected back
+//                    (k_opp_select); a random model's rows see zero logits (eval.rs:1749-1752)
+//   k_eval_sample    sample_with_temperature per row at word base + draw index
+//   env step         k_wide_step with the frozen mask and the outcome sink
+//   k_eval_finish    games recorded in env order up to the cap, seat -> checkpoint remap,
+//                    permutation rotation, move counts, freeze rule, RNG position
+//                    (eval.rs:1774-1869)
+// The RNG position lives on the device (as in the opponent-pool rollout).
+#include <algorithm>
+#include <cstring>
+#include <vector>
+#include "bppo_internal.h"
+#include "bppo_envs.h"
+#include "bppo_wide.h"
+#include "bppo_eval.h"
+
+namespace bppo {
+
+constexpr int EV_MAX_MODELS = 15;
+constexpr int EV_THREADS = 1024;
+constexpr int EV_ERR_ZERO_SUM = 16;   // d_err bit: the sampler's sum == 0.0 exit (bppo_eval.h temp_draws)
+
+// the step's small record, read by the host once per iteration
+struct EvalHdr {
+    int32_t games, active, ndraw, pad;
+    int32_t gbase[EV_MAX_MODELS + 2];   // group g (0 frozen, 1 + model) owns rows [gbase[g], gbase[g + 1])
+};
+
+struct EvalState {
+    int N, P, K, nperm, num_games;
+    bppo_eval::TempSched temp;
+    int32_t seat_model[BPPO_MAX_PLAYERS];
+    const int32_t *perm_tab;     // [nperm][P]: perm[player] = checkpoint
+    int32_t *perm_idx, *moves;   // [N]
+    uint8_t *frozen;             // [N]
+    int32_t *group, *gpos, *didx;   // [N]; didx: draw index or -1
+    float *tempv;                // [N]
+    EvalHdr *hdr;
+    uint64_t *rngpos;
+};
+
+// exclusive scan of a (rows, draws) pair packed in 64 bits over the block's threads in
+// thread order; *total = the block's sum.  wsum: one slot per wave.
+__device__ __forceinline__ uint64_t block_scan_excl(uint64_t v, uint64_t *wsum, uint64_t *total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    uint64_t inc = v;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t o = (uint64_t)__shfl_up((unsigned long long)inc, off, 64);
+        if (lane >= off) inc += o;
+    }
+    __syncthreads();               // the previous scan's readers are done with wsum
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint64_t base = 0, tot = 0;
+    for (int i = 0; i < nw; i++) {
+        const uint64_t s = wsum[i];
+        if (i < w) base += s;
+        tot += s;
+    }
+    *total = tot;
+    return base + inc - v;
+}
+
+// One block; thread t owns envs [t per, (t + 1) per) so any N is covered, in env order.
+__global__ void __launch_bounds__(EV_THREADS) k_eval_group(EvalState s, const int32_t *players) {
+    __shared__ uint64_t wsum[EV_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int per = (s.N + EV_THREADS - 1) / EV_THREADS;
+    const int e0 = min(s.N, tid * per), e1 = min(s.N, e0 + per);
+    for (int e = e0; e < e1; e++) {
+        int g = 0;
+        float temp = 0.0f;
+        int draws = 0;
+        if (!s.frozen[e]) {
+            const int cp = s.perm_tab[(size_t)s.perm_idx[e] * s.P + players[e]];   // eval.rs:1700-1701
+            g = 1 + s.seat_model[cp];                                               // :1704
+            temp = bppo_eval::get_temp(s.temp, s.moves[e]);                         // :1766
+            draws = bppo_eval::temp_draws(temp) ? 1 : 0;
+        }
+        s.group[e] = g;
+        s.tempv[e] = temp;
+        s.didx[e] = draws - 1;       // 0: draws (index below), -1: no draw
+    }
+    uint64_t rbase = 0, dbase = 0;   // rows / draws of the groups before g (the same in every thread)
+    for (int g = 0; g <= s.K; g++) {
+        uint32_t nr = 0, nd = 0;
+        for (int e = e0; e < e1; e++)
+            if (s.group[e] == g) { nr++; nd += s.didx[e] >= 0; }
+        uint64_t tot;
+        const uint64_t ex = block_scan_excl((uint64_t)nr | ((uint64_t)nd << 32), wsum, &tot);
+        uint32_t r = (uint32_t)rbase + (uint32_t)ex, d = (uint32_t)dbase + (uint32_t)(ex >> 32);
+        for (int e = e0; e < e1; e++)
+            if (s.group[e] == g) {
+                s.gpos[e] = (int32_t)r++;
+                if (s.didx[e] >= 0) s.didx[e] = (int32_t)d++;
+            }
+        if (tid == 0) s.hdr->gbase[g] = (int32_t)rbase;
+        rbase += (uint32_t)tot;
+        dbase += tot >> 32;
+    }
+    if (tid == 0) {
+        s.hdr->gbase[s.K + 1] = (int32_t)rbase;
+        s.hdr->ndraw = (int32_t)dbase;
+    }
+}
+
+struct EvalSampleArgs {
+    int N;
+    const float *logits;         // [N][A], env order
+    const uint8_t *mask;         // [N][A]
+    const int32_t *group;        // 0: frozen (writes nothing); 1 + model
+    const int32_t *didx;         // draw index or -1
+    const float *temp;           // [N]
+    uint32_t random_models;      // bit k: model k is the random player (zero logits)
+    Key8 key;
+    uint64_t stream, base;
+    const uint64_t *dbase;       // the step's first word position from device memory (else base)
+    int32_t *act;
+    int32_t *used;               // [N] whether the row drew (may be null)
+    int32_t *err;
+};
+
+// one row per lane; the row's word computed once; the sequential chains in registers
+template <int A>
+__global__ void __launch_bounds__(64) k_eval_sample(EvalSampleArgs g) {
+    __shared__ MathLds T;
+    T.load();
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= g.N) return;
+    const int grp = g.group ? g.group[e] : 1;
+    if (grp == 0) return;                                   // frozen: never sampled again
+    const bool rnd = (g.random_models >> (grp - 1)) & 1u;
+    float x[A];
+    uint8_t mk[A];
+#pragma unroll
+    for (int a = 0; a < A; a++) { mk[a] = g.mask[(size_t)e * A + a]; x[a] = g.logits[(size_t)e * A + a]; }
+    int first = -1;
+#pragma unroll
+    for (int a = 0; a < A; a++) {
+        const bool ok = mk[a] != 0;
+        if (ok && first < 0) first = a;
+        x[a] = ok ? (rnd ? 0.0f : x[a]) : -INFINITY;        // eval.rs:230-238, :1749-1752
+    }
+    const int di = g.didx[e];
+    uint32_t word = 0;
+    if (di >= 0) word = chacha12_word(g.key, g.stream, (g.dbase ? *g.dbase : g.base) + (uint64_t)di);
+    int used = 0;
+    const int a = bppo_eval::sample_with_temperature<A>(x, first < 0 ? 0 : first, g.temp[e], word, &used, T);
+    if (used != (di >= 0)) atomicOr(g.err, EV_ERR_ZERO_SUM);
+    g.act[e] = a;
+    if (g.used) g.used[e] = used;
+}
+
+static hipError_t eval_sample(int A, hipStream_t st, const EvalSampleArgs &g) {
+    const dim3 grid((g.N + 63) / 64), block(64);
+    if (A == C4_ACT) hipLaunchKernelGGL(k_eval_sample<C4_ACT>, grid, block, 0, st, g);
+    else if (A == LD_ACT) hipLaunchKernelGGL(k_eval_sample<LD_ACT>, grid, block, 0, st, g);
+    else if (A == SK_ACT) hipLaunchKernelGGL(k_eval_sample<SK_ACT>, grid, block, 0, st, g);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// rewards_to_placements (eval.rs:276-306) on n <= 6 rewards: a stable sort by reward
+// descending (incomparable pairs equal), then tie groups within 1e-6 of the group's first
+__device__ __forceinline__ void rewards_to_placements(const float *r, int n, int32_t *pl) {
+    int idx[BPPO_MAX_PLAYERS];
+    for (int i = 0; i < n; i++) idx[i] = i;
+    for (int i = 1; i < n; i++) {                 // insertion sort: stable
+        const int k = idx[i];
+        int j = i - 1;
+        while (j >= 0 && r[k] > r[idx[j]]) { idx[j + 1] = idx[j]; j--; }
+        idx[j + 1] = k;
+    }
+    int cur = 1, i = 0;
+    while (i < n) {
+        const float cr = r[idx[i]];
+        int tied = 0;
+        while (i + tied < n && fabsf(__fsub_rn(r[idx[i + tied]], cr)) < 1e-6f) tied++;
+        if (tied == 0) tied = 1;                  // a NaN reward ties with nothing, itself included
+        for (int j = 0; j < tied; j++) pl[idx[i + j]] = cur;
+        cur += tied;
+        i += tied;
+    }
+}
+
+// After the env step (eval.rs:1774-1869).  One block, thread t owns envs [t per, (t + 1) per).
+__global__ void __launch_bounds__(EV_THREADS) k_eval_finish(EvalState s, int step, const uint8_t *done,
+                                                            const EvalOutcome *sink, bppo_eval_game *games,
+                                                            int games_cap) {
+    __shared__ uint64_t wsum[EV_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int per = (s.N + EV_THREADS - 1) / EV_THREADS;
+    const int e0 = min(s.N, tid * per), e1 = min(s.N, e0 + per);
+    const int g0 = s.hdr->games;
+    uint32_t nd = 0, na = 0;
+    for (int e = e0; e < e1; e++) { nd += done[e] != 0; na += s.frozen[e] == 0; }
+    uint64_t tot;
+    const uint64_t ex = block_scan_excl((uint64_t)nd | ((uint64_t)na << 32), wsum, &tot);   // (hdr read above: barrier inside)
+    const int ND = (int)(uint32_t)tot, ACT = (int)(tot >> 32);
+    // finished games are recorded in env order while games_completed < num_games (:1783-1789)
+    const int nrec = min(ND, max(0, s.num_games - g0));
+    const int g1 = g0 + nrec;
+    // freeze rule (:1841-1869): active > remaining freezes the excess, this step's finished
+    // envs first (env order), then any non-frozen env in index order
+    const int remaining = max(0, s.num_games - g1);
+    const int to_freeze = ACT > remaining ? ACT - remaining : 0;
+    const int f1 = min(to_freeze, ND), f2 = to_freeze - f1;
+    int k = (int)(uint32_t)ex;
+    uint32_t alive = 0;
+    for (int e = e0; e < e1; e++) {
+        int mv = s.moves[e] + 1;                                    // every env, frozen included (:1775-1777)
+        if (done[e]) {
+            if (k < nrec) {
+                const int pi = s.perm_idx[e];
+                const int32_t *perm = s.perm_tab + (size_t)pi * s.P;
+                const EvalOutcome o = sink[e];
+                bppo_eval_game rec;
+                for (int c = 0; c < BPPO_MAX_PLAYERS; c++) { rec.total_reward[c] = 0.0f; rec.placement[c] = 0; }
+                for (int c = 0; c < s.P; c++) {                     // checkpoint c sat on seat p (:1798-1821)
+                    int p = 0;
+                    for (int q = 0; q < s.P; q++) p = perm[q] == c ? q : p;
+                    rec.total_reward[c] = o.total_reward[p];
+                    rec.placement[c] = o.placement[p];
+                }
+                if (!o.has_outcome) rewards_to_placements(rec.total_reward, s.P, rec.placement);   // :1822-1825
+                rec.length = o.length; rec.env_index = e; rec.perm_index = pi; rec.step = step;
+                if (g0 + k < games_cap) games[g0 + k] = rec;
+                mv = 0;                                              // :1830
+                s.perm_idx[e] = (pi + 1) % s.nperm;                  // :1831
+            }                                                        // past the cap: dropped, nothing touched (:1785-1787)
+            if (k < f1) s.frozen[e] = 1;
+            k++;
+        }
+        s.moves[e] = mv;
+        alive += s.frozen[e] == 0;
+    }
+    if (f2 > 0) {                                                   // the same in every thread
+        uint64_t t2;
+        int r = (int)(uint32_t)block_scan_excl((uint64_t)alive, wsum, &t2);
+        for (int e = e0; e < e1; e++)
+            if (!s.frozen[e]) {
+                if (r < f2) s.frozen[e] = 1;
+                r++;
+            }
+    }
+    if (tid == 0) {
+        s.hdr->games = g1;
+        s.hdr->active = ACT - to_freeze;
+        *s.rngpos += (uint64_t)s.hdr->ndraw;                       // the step's draws
+    }
+}
+
+__global__ void k_eval_init(EvalState s, uint64_t pos) {
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < s.N; e += gridDim.x * blockDim.x) {
+        s.perm_idx[e] = e % s.nperm;          // eval.rs:1662
+        s.moves[e] = 0;
+        s.frozen[e] = 0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        s.hdr->games = 0;
+        s.hdr->active = s.N;
+        s.hdr->ndraw = 0;
+        *s.rngpos = pos;
+    }
+}
+
+// generate_permutations / heap_permute (eval.rs:1591-1612), exactly as written
+static void heap_permute(int32_t *arr, int k, int n, std::vector<int32_t> &out) {
+    if (k == 1) { out.insert(out.end(), arr, arr + n); return; }
+    heap_permute(arr, k - 1, n, out);
+    for (int i = 0; i < k - 1; i++) {
+        if (k % 2 == 0) std::swap(arr[i], arr[k - 1]);
+        else std::swap(arr[0], arr[k - 1]);
+        heap_permute(arr, k - 1, n, out);
+    }
+}
+static std::vector<int32_t> generate_permutations(int n) {
+    std::vector<int32_t> out;
+    int32_t arr[BPPO_MAX_PLAYERS];
+    for (int i = 0; i < n; i++) arr[i] = i;
+    heap_permute(arr, n, n, out);
+    return out;
+}
+
+// device memory of one evaluation, freed when it ends
+struct EvalBuffers {
+    std::vector<void *> dev;
+    EvalHdr *h_hdr = nullptr;
+    template <class T>
+    hipError_t alloc(T **p, size_t n) {
+        *p = nullptr;
+        const hipError_t e = hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T));
+        if (e == hipSuccess) dev.push_back(*p);
+        return e;
+    }
+    ~EvalBuffers() {
+        for (void *p : dev) (void)hipFree(p);
+        if (h_hdr) (void)hipHostFree(h_hdr);
+    }
+};
+
+struct HostMath {
+    float expf(float v) const { return bppo_math::expf_glibc(v); }
+};
+
+template <int A>
+static void sample_rows_host(int B, const float *logits, const uint8_t *masks, const float *temps, const Key8 &key,
+                             uint64_t stream, uint64_t pos, int32_t *actions, int32_t *used_out) {
+    const HostMath T;
+    for (int b = 0; b < B; b++) {
+        float x[A];
+        int first = -1;
+        for (int a = 0; a < A; a++) {
+            const bool ok = masks[(size_t)b * A + a] != 0;
+            if (ok && first < 0) first = a;
+            x[a] = ok ? logits[(size_t)b * A + a] : -INFINITY;
+        }
+        uint32_t blk[16];
+        chacha12_block(key, pos >> 4, stream, blk);
+        int used = 0;
+        actions[b] = bppo_eval::sample_with_temperature<A>(x, first < 0 ? 0 : first, temps[b], blk[pos & 15], &used, T);
+        pos += (uint64_t)used;
+        if (used_out) used_out[b] = used;
+    }
+}
+
+}  // namespace bppo
+
+using namespace bppo;
+
+extern "C" size_t bppo_eval_config_size(void) { return sizeof(bppo_eval_config); }
+extern "C" size_t bppo_eval_game_size(void) { return sizeof(bppo_eval_game); }
+
+extern "C" bppo_status bppo_debug_eval_perms(int32_t n, int32_t *out) {
+    if (!out || n < 1 || n > BPPO_MAX_PLAYERS) return BPPO_ERR_ARG;
+    const std::vector<int32_t> t = generate_permutations(n);
+    std::memcpy(out, t.data(), sizeof(int32_t) * t.size());
+    return BPPO_OK;
+}
+
+extern "C" bppo_status bppo_debug_eval_sample(int32_t device, int32_t A, int32_t B, const float *logits,
+                                              const uint8_t *masks, const float *temps, uint64_t seed,
+                                              uint64_t stream, uint64_t word_pos, int32_t *actions,
+                                              int32_t *draws_used) {
+    if (!logits || !masks || !temps || !actions || B <= 0 || (A != C4_ACT && A != LD_ACT && A != SK_ACT))
+        return BPPO_ERR_ARG;
+    const Key8 key = seed_key(seed);
+    if (!device) {
+        if (A == C4_ACT) sample_rows_host<C4_ACT>(B, logits, masks, temps, key, stream, word_pos, actions, draws_used);
+        else if (A == LD_ACT) sample_rows_host<LD_ACT>(B, logits, masks, temps, key, stream, word_pos, actions, draws_used);
+        else sample_rows_host<SK_ACT>(B, logits, masks, temps, key, stream, word_pos, actions, draws_used);
+        return BPPO_OK;
+    }
+    // the rows' draw indices in row order, as k_eval_group's second prefix gives them
+    std::vector<int32_t> didx((size_t)B);
+    int32_t nd = 0;
+    for (int b = 0; b < B; b++) didx[b] = bppo_eval::temp_draws(temps[b]) ? nd++ : -1;
+    const size_t nA = (size_t)B * A;
+    EvalBuffers buf;
+    float *d_l = nullptr, *d_t = nullptr;
+    uint8_t *d_m = nullptr;
+    int32_t *d_di = nullptr, *d_a = nullptr, *d_u = nullptr, *d_e = nullptr;
+    int32_t err = 0;
+    if (buf.alloc(&d_l, nA) != hipSuccess || buf.alloc(&d_m, nA) != hipSuccess || buf.alloc(&d_t, (size_t)B) != hipSuccess ||
+        buf.alloc(&d_di, (size_t)B) != hipSuccess || buf.alloc(&d_a, (size_t)B) != hipSuccess ||
+        buf.alloc(&d_u, (size_t)B) != hipSuccess || buf.alloc(&d_e, 1) != hipSuccess)
+        return BPPO_ERR_HIP;
+    if (hipMemcpy(d_l, logits, nA * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_m, masks, nA, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_t, temps, 4ull * B, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_di, didx.data(), 4ull * B, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(d_e, 0, 4) != hipSuccess)
+        return BPPO_ERR_HIP;
+    EvalSampleArgs g;
+    g.N = B; g.logits = d_l; g.mask = d_m; g.group = nullptr; g.didx = d_di; g.temp = d_t; g.random_models = 0;
+    g.key = key; g.stream = stream; g.base = word_pos; g.dbase = nullptr; g.act = d_a; g.used = d_u; g.err = d_e;
+    if (eval_sample(A, nullptr, g) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(actions, d_a, 4ull * B, hipMemcpyDeviceToHost) != hipSuccess ||
+        (draws_used && hipMemcpy(draws_used, d_u, 4ull * B, hipMemcpyDeviceToHost) != hipSuccess) ||
+        hipMemcpy(&err, d_e, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return BPPO_ERR_HIP;
+    return (err & EV_ERR_ZERO_SUM) ? BPPO_ERR_NONFINITE : BPPO_OK;
+}
+
+extern "C" bppo_status bppo_evaluate(bppo_ctx *c, const bppo_eval_config *cfg, int32_t n_models, const float *params,
+                                     const double *norm_mean, const double *norm_m2, const double *norm_count,
+                                     const int32_t *is_random, const int32_t *seat_model, int32_t n_checkpoints,
+                                     bppo_eval_game *games, int32_t cap, int32_t *n_games, uint64_t *rng_word_pos) {
+    if (!c) return BPPO_ERR_ARG;
+    if (!c->wide || c->cfg.env_kind == BPPO_ENV_CARTPOLE) {
+        c->err = "evaluate: multi-player envs only (no stats mode for CartPole)";
+        return BPPO_ERR_UNSUPPORTED;
+    }
+    if (!cfg || !seat_model || !n_games || (cap > 0 && !games) || cap < 0) { c->err = "evaluate: NULL argument"; return BPPO_ERR_ARG; }
+    if (cfg->num_games < 0 || cfg->max_steps < 0) { c->err = "evaluate: num_games and max_steps must not be negative"; return BPPO_ERR_ARG; }
+    if (n_models < 1 || n_models > EV_MAX_MODELS) { c->err = "evaluate: 1..15 models"; return BPPO_ERR_ARG; }
+    const int P = c->Pa, N = c->N, A = c->A, D = c->D, L = c->L, K = n_models;
+    // the reference's permutations are over 0..num_players and a further checkpoint panics
+    // (eval.rs:1801-1804), fewer fail its assert (:1640-1643)
+    if (n_checkpoints != P) { c->err = "evaluate: n_checkpoints must equal the seated player count"; return BPPO_ERR_ARG; }
+    uint32_t random_models = 0;
+    for (int k = 0; k < K; k++)
+        if (is_random && is_random[k]) random_models |= 1u << k;
+    for (int p = 0; p < P; p++)
+        if (seat_model[p] < 0 || seat_model[p] >= K) { c->err = "evaluate: seat_model names a model out of range"; return BPPO_ERR_ARG; }
+    if (random_models != (1u << K) - 1u && !params) { c->err = "evaluate: model parameters required"; return BPPO_ERR_ARG; }
+    drop_prefetch(c);
+    if (!c->gae_done) c->collected = 0;       // a rollout not yet bootstrapped would read the evaluation's envs
+    *n_games = 0;
+
+    // RNG (eval.rs:1646-1648): base_seed = rng.next_u64(), words 0 and 1, low word first
+    const Key8 key = seed_key(cfg->seed);
+    uint32_t blk0[16];
+    chacha12_block(key, 0, 0, blk0);
+    const uint64_t base_seed = ((uint64_t)blk0[1] << 32) | (uint64_t)blk0[0];
+
+    const std::vector<int32_t> perms = generate_permutations(P);
+    const int nperm = (int)(perms.size() / (size_t)P);
+    const size_t np = c->net.n_params;
+
+    EvalBuffers buf;
+    EvalState s{};
+    int32_t *d_perm_tab = nullptr;
+    float *d_params = nullptr, *d_oxc = nullptr, *d_ologits = nullptr;
+    double *d_on = nullptr;
+    EvalOutcome *d_sink = nullptr;
+    bppo_eval_game *d_games = nullptr;
+    const int games_cap = std::min(cap, cfg->num_games);
+    BPPO_HIP(c, buf.alloc(&d_perm_tab, perms.size()));
+    BPPO_HIP(c, buf.alloc(&s.perm_idx, (size_t)N));
+    BPPO_HIP(c, buf.alloc(&s.moves, (size_t)N));
+    BPPO_HIP(c, buf.alloc(&s.frozen, (size_t)N));
+    BPPO_HIP(c, buf.alloc(&s.group, (size_t)N));
+    BPPO_HIP(c, buf.alloc(&s.gpos, (size_t)N));
+    BPPO_HIP(c, buf.alloc(&s.didx, (size_t)N));
+    BPPO_HIP(c, buf.alloc(&s.tempv, (size_t)N));
+    BPPO_HIP(c, buf.alloc(&s.hdr, 1));
+    BPPO_HIP(c, buf.alloc(&s.rngpos, 1));
+    BPPO_HIP(c, buf.alloc(&d_params, np * K));
+    BPPO_HIP(c, buf.alloc(&d_on, (size_t)(2 * D + 1) * K));
+    BPPO_HIP(c, buf.alloc(&d_oxc, (size_t)N * L));
+    BPPO_HIP(c, buf.alloc(&d_ologits, (size_t)N * A));
+    BPPO_HIP(c, buf.alloc(&d_sink, (size_t)N));
+    BPPO_HIP(c, buf.alloc(&d_games, (size_t)games_cap));
+    BPPO_HIP(c, hipHostMalloc((void **)&buf.h_hdr, sizeof(EvalHdr)));
+    s.N = N; s.P = P; s.K = K; s.nperm = nperm; s.num_games = cfg->num_games;
+    s.temp = bppo_eval::TempSched{cfg->temp_initial, cfg->temp_final, cfg->temp_cutoff, cfg->temp_decay};
+    for (int p = 0; p < BPPO_MAX_PLAYERS; p++) s.seat_model[p] = p < P ? seat_model[p] : 0;
+    s.perm_tab = d_perm_tab;
+
+    // models: uploads ordered on the context's stream, drained before the host arrays may go
+    std::vector<int> has_norm((size_t)K, 0);
+    std::vector<double> on((size_t)(2 * D + 1) * K, 0.0);
+    for (int k = 0; k < K; k++) {
+        if ((random_models >> k) & 1u) continue;
+        BPPO_HIP(c, hipMemcpyAsync(d_params + (size_t)k * np, params + (size_t)k * np, sizeof(float) * np,
+                                   hipMemcpyHostToDevice, c->stream));
+        if (!norm_count || norm_count[k] < 2.0 || !norm_mean || !norm_m2) continue;
+        has_norm[k] = 1;
+        std::memcpy(&on[(size_t)k * (2 * D + 1)], norm_mean + (size_t)k * D, sizeof(double) * D);
+        std::memcpy(&on[(size_t)k * (2 * D + 1) + D], norm_m2 + (size_t)k * D, sizeof(double) * D);
+        on[(size_t)k * (2 * D + 1) + 2 * D] = norm_count[k];
+    }
+    BPPO_HIP(c, hipMemcpyAsync(d_on, on.data(), sizeof(double) * on.size(), hipMemcpyHostToDevice, c->stream));
+    BPPO_HIP(c, hipMemcpyAsync(d_perm_tab, perms.data(), sizeof(int32_t) * perms.size(), hipMemcpyHostToDevice, c->stream));
+    BPPO_HIP(c, hipMemsetAsync(c->d_err, 0, 4, c->stream));
+    BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
+    hipLaunchKernelGGL(k_eval_init, dim3(std::min((N + 255) / 256, 1024)), dim3(256), 0, c->stream, s, (uint64_t)2);
+    TRY(launch_check(c, "k_eval_init"));
+    // VecEnv::new (E::new(base_seed + i) and a reset), then set_all_num_players resets every
+    // env again (env.rs:281-302, 313-326); E::new's reward shaping is the zero schedule
+    // (liars_dice.rs:461-463, skull.rs:1062-1065); Skull is seated with the context's player_count
+    BPPO_HIP(c, wide_env_reset(c->cfg.env_kind, c->stream, N, base_seed, P, c->d_wstate, c->d_env_pos, c->d_ep_ret,
+                               c->d_ep_len));
+    BPPO_HIP(c, wide_env_reset_again(c->cfg.env_kind, c->stream, N, base_seed, c->d_wstate, c->d_env_pos));
+
+    auto observe_group = [&]() -> bppo_status {
+        BPPO_HIP(c, wide_env_observe(c->cfg.env_kind, c->G > 0, c->stream, N, c->d_wstate, c->d_bxc, c->d_bmask,
+                                     c->d_bplayers));
+        hipLaunchKernelGGL(k_eval_group, dim3(1), dim3(EV_THREADS), 0, c->stream, s, c->d_bplayers);
+        TRY(launch_check(c, "k_eval_group"));
+        BPPO_HIP(c, hipMemcpyAsync(buf.h_hdr, s.hdr, sizeof(EvalHdr), hipMemcpyDeviceToHost, c->stream));
+        BPPO_HIP(c, hipStreamSynchronize(c->stream));
+        return BPPO_OK;
+    };
+    TRY(observe_group());
+    bppo_status st = BPPO_OK;
+    for (int step = 0;; step++) {
+        const EvalHdr &h = *buf.h_hdr;
+        if (h.games >= cfg->num_games || h.active == 0) break;        // eval.rs:1670-1674
+        if (step >= cfg->max_steps) { c->err = "evaluate: max_steps exceeded before num_games games were played"; st = BPPO_ERR_ARG; break; }
+        const int32_t *gb = h.gbase;
+        bool any_fwd = false;
+        for (int k = 0; k < K; k++) any_fwd = any_fwd || (!((random_models >> k) & 1u) && gb[k + 2] > gb[k + 1]);
+        if (any_fwd) {
+            TRY(opp_sort_rows(c, s.group, s.gpos, c->d_bxc, d_oxc));
+            for (int k = 0; k < K; k++) {
+                const int r0 = gb[k + 1], rows = gb[k + 2] - gb[k + 1];
+                if (rows <= 0 || ((random_models >> k) & 1u)) continue;
+                float *x = d_oxc + (size_t)r0 * L;
+                if (has_norm[k]) TRY(launch_obs_norm_rows_on(c, rows, x + c->G, L, nullptr, d_on + (size_t)k * (2 * D + 1)));
+                TRY(wide_forward_actor(c, rows, x, L, d_params + (size_t)k * np, d_ologits + (size_t)r0 * A));
+            }
+            TRY(opp_select(c, s.group, s.gpos, d_ologits, c->d_logits));
+        }
+        EvalSampleArgs g;
+        g.N = N; g.logits = c->d_logits; g.mask = c->d_bmask; g.group = s.group; g.didx = s.didx; g.temp = s.tempv;
+        g.random_models = random_models; g.key = key; g.stream = 0; g.base = 0; g.dbase = s.rngpos;
+        g.act = c->d_act_in; g.used = nullptr; g.err = c->d_err;
+        BPPO_HIP(c, eval_sample(A, c->stream, g));
+        WideStepArgs w;
+        w.N = N; w.t = step; w.state = c->d_wstate; w.env_pos = c->d_env_pos; w.seed_base = base_seed;
+        w.actions = c->d_act_in; w.shaping = 0.0f;
+        w.all_r = nullptr; w.rew_act = nullptr; w.done_f = nullptr; w.done_u8 = c->d_scr_d;
+        w.ep_ret = c->d_ep_ret; w.ep_len = c->d_ep_len; w.eps = c->d_eps; w.ep_count = c->d_ep_count;
+        w.eps_cap = 0; w.err = c->d_err;
+        w.frozen = s.frozen; w.sink = d_sink;
+        BPPO_HIP(c, wide_env_step(c->cfg.env_kind, c->stream, w));
+        hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(EV_THREADS), 0, c->stream, s, step, c->d_scr_d, d_sink, d_games,
+                           games_cap);
+        TRY(launch_check(c, "k_eval_finish"));
+        TRY(observe_group());
+    }
+    // results: the games, the RNG position, the error flags; the episode counter back to zero
+    const int ng = std::min<int>(buf.h_hdr->games, games_cap);
+    uint64_t pos = 0;
+    int32_t err = 0;
+    if (ng > 0) BPPO_HIP(c, hipMemcpyAsync(games, d_games, sizeof(bppo_eval_game) * (size_t)ng, hipMemcpyDeviceToHost, c->stream));
+    BPPO_HIP(c, hipMemcpyAsync(&pos, s.rngpos, 8, hipMemcpyDeviceToHost, c->stream));
+    BPPO_HIP(c, hipMemcpyAsync(&err, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
+    BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
+    BPPO_HIP(c, hipStreamSynchronize(c->stream));
+    *n_games = buf.h_hdr->games;
+    if (rng_word_pos) *rng_word_pos = pos;
+    if (st != BPPO_OK) return st;
+    if (err & 8) { c->err = "evaluate: an action outside the env's action mask"; return BPPO_ERR_ARG; }
+    if (err & EV_ERR_ZERO_SUM) { c->err = "evaluate: the sampler's softmax sum was zero"; return BPPO_ERR_NONFINITE; }
+    return BPPO_OK;
+}

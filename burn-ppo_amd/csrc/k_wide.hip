@@ -44,6 +44,7 @@ template <> struct EnvT<BPPO_ENV_CARTPOLE> {
     }
     __device__ static void priv(const S &, float *) {}
     __device__ static void mask(const S &, uint8_t *m) { m[0] = 1; m[1] = 1; }
+    __device__ static bool outcome(const S &, int32_t out[6]) { for (int p = 0; p < 6; p++) out[p] = 0; return false; }
 };
 template <> struct EnvT<BPPO_ENV_CONNECT_FOUR> {
     using S = C4State;
@@ -58,6 +59,7 @@ template <> struct EnvT<BPPO_ENV_CONNECT_FOUR> {
     __device__ static void obs(const S &s, float *row) { c4_obs(s, row); }
     __device__ static void priv(const S &, float *) {}
     __device__ static void mask(const S &s, uint8_t *m) { c4_mask(s, m); }
+    __device__ static bool outcome(const S &s, int32_t out[6]) { return c4_outcome(s, out); }
 };
 template <> struct EnvT<BPPO_ENV_LIARS_DICE> {
     using S = LDState;
@@ -84,6 +86,7 @@ template <> struct EnvT<BPPO_ENV_LIARS_DICE> {
     __device__ static void obs(const S &s, float *row) { ld_obs(s, row); }
     __device__ static void priv(const S &s, float *row) { ld_priv(s, row); }
     __device__ static void mask(const S &s, uint8_t *m) { ld_mask(s, m); }
+    __device__ static bool outcome(const S &s, int32_t out[6]) { return ld_outcome(s, out); }
 };
 template <> struct EnvT<BPPO_ENV_SKULL> {
     using S = SKState;
@@ -101,6 +104,7 @@ template <> struct EnvT<BPPO_ENV_SKULL> {
     __device__ static void obs(const S &s, float *row) { sk_obs(s, row); }
     __device__ static void priv(const S &s, float *row) { sk_priv(s, row); }
     __device__ static void mask(const S &s, uint8_t *m) { sk_mask(s, m); }
+    __device__ static bool outcome(const S &s, int32_t out[6]) { return sk_outcome(s, out); }
 };
 
 template <int ENV>
@@ -123,6 +127,20 @@ __global__ void k_wide_reset(int N, uint64_t seed_base, int players, void *state
     env_pos[e] = pos;
     for (int p = 0; p < E::P; p++) ep_ret[(size_t)e * E::P + p] = 0.0f;
     ep_len[e] = 0;
+}
+
+// VecEnv::set_all_num_players (env.rs:313-326): every env reset once more, from its
+// own RNG position, fixed-player games included (only set_num_players is a no-op there)
+template <int ENV>
+__global__ void k_wide_reset_again(int N, uint64_t seed_base, void *state, uint64_t *env_pos) {
+    using E = EnvT<ENV>;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    typename E::S s = env_state<ENV>(state)[e];
+    uint64_t pos = env_pos[e];
+    E::reset(s, seed_key(seed_base + (uint64_t)e), pos);
+    env_state<ENV>(state)[e] = s;
+    env_pos[e] = pos;
 }
 
 // get_privileged_obs / get_observations / get_action_masks / get_current_players
@@ -163,32 +181,54 @@ __global__ void __launch_bounds__(64) k_wide_observe(int N, const void *state, f
 // VecEnv::step (env.rs:400-487) + the reward bookkeeping of collect_rollouts
 // (ppo.rs:382-428, return normalisation off): all_rewards [N][P], the acting
 // player's reward, done flag, episode accumulators, completed-episode records
-// and auto-reset.
-template <int ENV>
+// and auto-reset.  EVAL (eval.hip, run_stats_mode_env): an env marked terminal is
+// skipped entirely (env.rs:429-432) -- its lane still joins wave_episode_slot, not
+// done -- and a finished game's totals and game_outcome go to the sink before the
+// reset (env.rs:442-450).  The training launches instantiate EVAL = false.
+template <int ENV, bool EVAL>
 __global__ void k_wide_step(WideStepArgs a) {
     using E = EnvT<ENV>;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.N) return;
-    typename E::S s = env_state<ENV>(a.state)[e];
-    const int act = a.actions[e];
-    const int p_act = E::player(s);
-    const Key8 k = seed_key(a.seed_base + (uint64_t)e);
-    uint64_t pos = a.env_pos[e];
-    float r[BPPO_MAX_PLAYERS] = {0, 0, 0, 0, 0, 0};
-    int done = 0, bad = 0;
-    E::step(s, act, a.shaping, r, done, bad, k, pos);
-    if (bad && a.err) atomicOr(a.err, 8);
-    float *er = a.ep_ret + (size_t)e * E::P;
-    for (int p = 0; p < E::P; p++) {
-        er[p] = __fadd_rn(er[p], r[p]);
-        if (a.all_r) a.all_r[(size_t)e * E::P + p] = r[p];
+    bool frozen = false;
+    if constexpr (EVAL) frozen = a.frozen[e] != 0;
+    typename E::S s;
+    Key8 k;
+    uint64_t pos = 0;
+    float *er = nullptr;
+    int len = 0, done = 0;
+    if (!frozen) {
+        s = env_state<ENV>(a.state)[e];
+        const int act = a.actions[e];
+        const int p_act = E::player(s);
+        k = seed_key(a.seed_base + (uint64_t)e);
+        pos = a.env_pos[e];
+        float r[BPPO_MAX_PLAYERS] = {0, 0, 0, 0, 0, 0};
+        int bad = 0;
+        E::step(s, act, a.shaping, r, done, bad, k, pos);
+        if (bad && a.err) atomicOr(a.err, 8);
+        er = a.ep_ret + (size_t)e * E::P;
+        for (int p = 0; p < E::P; p++) {
+            er[p] = __fadd_rn(er[p], r[p]);
+            if (a.all_r) a.all_r[(size_t)e * E::P + p] = r[p];
+        }
+        len = a.ep_len[e] + 1;
+        if (a.rew_act) a.rew_act[e] = r[p_act];
+        if (a.done_f) a.done_f[e] = done ? 1.0f : 0.0f;
+        if (a.done_u8) a.done_u8[e] = (uint8_t)done;
+    } else if (a.done_u8) {
+        a.done_u8[e] = 0;
     }
-    const int len = a.ep_len[e] + 1;
-    if (a.rew_act) a.rew_act[e] = r[p_act];
-    if (a.done_f) a.done_f[e] = done ? 1.0f : 0.0f;
-    if (a.done_u8) a.done_u8[e] = (uint8_t)done;
+    // (a frozen lane takes part here too, not done)
     const int slot = wave_episode_slot(done != 0, a.ep_count);
     if (done) {
+        if constexpr (EVAL) {
+            EvalOutcome o;
+            for (int p = 0; p < BPPO_MAX_PLAYERS; p++) o.total_reward[p] = p < E::P ? er[p] : 0.0f;
+            o.length = len;
+            o.has_outcome = E::outcome(s, o.placement) ? 1 : 0;
+            a.sink[e] = o;
+        }
         if (slot < a.eps_cap) {
             EpisodeRec rec;
             for (int p = 0; p < BPPO_MAX_PLAYERS; p++) rec.total_reward[p] = p < E::P ? er[p] : 0.0f;
@@ -198,11 +238,13 @@ __global__ void k_wide_step(WideStepArgs a) {
         for (int p = 0; p < E::P; p++) er[p] = 0.0f;
         a.ep_len[e] = 0;
         E::reset(s, k, pos);
-    } else {
+    } else if (!frozen) {
         a.ep_len[e] = len;
     }
-    env_state<ENV>(a.state)[e] = s;
-    a.env_pos[e] = pos;
+    if (!frozen) {
+        env_state<ENV>(a.state)[e] = s;
+        a.env_pos[e] = pos;
+    }
 }
 
 // apply_action_mask + sample_categorical + log_prob_categorical (ppo.rs:337-366):
@@ -487,7 +529,26 @@ hipError_t wide_env_observe(int kind, int with_priv, hipStream_t st, int N, cons
 }
 
 hipError_t wide_env_step(int kind, hipStream_t st, const WideStepArgs &a) {
-    ENV_DISPATCH(kind, k_wide_step, dim3((a.N + 255) / 256), dim3(256), a);
+    const dim3 grid((a.N + 255) / 256), block(256);
+    const bool ev = a.frozen != nullptr && a.sink != nullptr;
+    if (kind == BPPO_ENV_CONNECT_FOUR) {
+        if (ev) hipLaunchKernelGGL((k_wide_step<BPPO_ENV_CONNECT_FOUR, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_wide_step<BPPO_ENV_CONNECT_FOUR, false>), grid, block, 0, st, a);
+    } else if (kind == BPPO_ENV_CARTPOLE) {
+        if (ev) return hipErrorInvalidValue;     // no stats mode for CartPole
+        hipLaunchKernelGGL((k_wide_step<BPPO_ENV_CARTPOLE, false>), grid, block, 0, st, a);
+    } else if (kind == BPPO_ENV_SKULL) {
+        if (ev) hipLaunchKernelGGL((k_wide_step<BPPO_ENV_SKULL, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_wide_step<BPPO_ENV_SKULL, false>), grid, block, 0, st, a);
+    } else {
+        if (ev) hipLaunchKernelGGL((k_wide_step<BPPO_ENV_LIARS_DICE, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_wide_step<BPPO_ENV_LIARS_DICE, false>), grid, block, 0, st, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t wide_env_reset_again(int kind, hipStream_t st, int N, uint64_t seed_base, void *state, uint64_t *env_pos) {
+    ENV_DISPATCH(kind, k_wide_reset_again, dim3((N + 255) / 256), dim3(256), N, seed_base, state, env_pos);
     return hipGetLastError();
 }
 

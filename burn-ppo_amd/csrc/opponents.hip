@@ -302,12 +302,7 @@ bppo_status opp_step_forwards(bppo_ctx *c) {
     const size_t np = c->net.n_params;
     const int32_t *gb = c->h_gbase;            // group g owns draw rows [gb[g], gb[g + 1])
     if (gb[c->opp_K + 1] == gb[1]) return BPPO_OK;   // no opponent moves this step
-    {
-        const size_t n = (size_t)c->N * c->L;
-        hipLaunchKernelGGL(k_opp_sort_rows, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0,
-                           c->stream, c->N, c->L, c->d_group, c->d_gpos, c->d_oraw, c->d_oxc);
-        TRY(launch_check(c, __func__));
-    }
+    TRY(opp_sort_rows(c, c->d_group, c->d_gpos, c->d_oraw, c->d_oxc));
     for (int k = 0; k < c->opp_K; k++) {
         const int r0 = gb[k + 1], rows = gb[k + 2] - gb[k + 1];
         if (rows <= 0) continue;
@@ -316,9 +311,21 @@ bppo_status opp_step_forwards(bppo_ctx *c) {
             TRY(launch_obs_norm_rows_on(c, rows, x + c->G, c->L, nullptr, c->d_opp_on + (size_t)k * (2 * c->D + 1)));
         TRY(wide_forward_actor(c, rows, x, c->L, c->d_opp_params + (size_t)k * np, c->d_ologits + (size_t)r0 * c->A));
     }
+    return opp_select(c, c->d_group, c->d_gpos, c->d_ologits, c->d_logits);
+}
+
+// the two row movers, also used by the evaluation loop (eval.hip): rows of group 0 stay
+bppo_status opp_sort_rows(bppo_ctx *c, const int32_t *group, const int32_t *gpos, const float *src, float *dst) {
+    const size_t n = (size_t)c->N * c->L;
+    hipLaunchKernelGGL(k_opp_sort_rows, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0,
+                       c->stream, c->N, c->L, group, gpos, src, dst);
+    TRY(launch_check(c, __func__));
+    return BPPO_OK;
+}
+bppo_status opp_select(bppo_ctx *c, const int32_t *group, const int32_t *gpos, const float *src, float *dst) {
     const int n = c->N * c->A;
-    hipLaunchKernelGGL(k_opp_select, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->N, c->A, c->d_group,
-                       c->d_gpos, c->d_ologits, c->d_logits);
+    hipLaunchKernelGGL(k_opp_select, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->N, c->A, group, gpos, src,
+                       dst);
     TRY(launch_check(c, __func__));
     return BPPO_OK;
 }

@@ -117,6 +117,27 @@ typedef struct {
     float value_norm_target_mean, value_norm_target_std, value_norm_rescale_mag;
 } bppo_update_metrics;
 
+/* stats-mode evaluation (eval.rs:1621-1877), see bppo_evaluate */
+typedef struct {
+    int32_t num_games;           /* games to record */
+    int32_t max_steps;           /* hard cap on loop iterations (VecEnv steps): BPPO_ERR_ARG beyond it */
+    uint64_t seed;               /* StdRng::seed_from_u64(seed) of the evaluation */
+    float temp_initial;          /* TempSchedule (eval.rs:110-216) */
+    float temp_final;
+    int32_t temp_cutoff;         /* move number of the cutoff; -1 = None (constant temp_initial) */
+    int32_t temp_decay;          /* 1: linear decay initial -> final over temp_cutoff moves */
+} bppo_eval_config;
+
+/* one recorded game; indexed by checkpoint, not by seat (eval.rs:1798-1821) */
+typedef struct {
+    float total_reward[BPPO_MAX_PLAYERS];   /* checkpoints >= n_checkpoints: 0 */
+    int32_t placement[BPPO_MAX_PLAYERS];    /* 1 = first; ties share a placement */
+    int32_t length;              /* moves of the game */
+    int32_t env_index;
+    int32_t perm_index;          /* the seat permutation it was played under */
+    int32_t step;                /* loop iteration at which it ended */
+} bppo_eval_game;
+
 typedef struct bppo_ctx bppo_ctx;
 
 /* ---- lifecycle ---------------------------------------------------------- */
@@ -132,6 +153,8 @@ size_t bppo_config_size(void);
 size_t bppo_update_metrics_size(void);
 size_t bppo_episode_size(void);
 size_t bppo_rollout_info_size(void);
+size_t bppo_eval_config_size(void);
+size_t bppo_eval_game_size(void);
 
 /* ---- ActorCritic -------------------------------------------------------- */
 /* flat parameters in Burn record order: per Linear W[in][out] then b[out];
@@ -278,6 +301,37 @@ bppo_status bppo_opponents_set(bppo_ctx *ctx, int32_t n_models, const float *par
 /* the seat state after the last rollout's reshuffles */
 bppo_status bppo_opponents_get_envs(bppo_ctx *ctx, int32_t *learner_pos, int32_t *pos_to_opp);
 
+/* Stats-mode evaluation on the device (eval.rs:1621-1877 run_stats_mode_env, the engine of
+ * `eval --num-games` and of the tournament pods): plays cfg->num_games games between
+ * checkpoints on this context's VecEnv (num_envs parallel games), sampling every move with
+ * the temperature schedule (sample_with_temperature, eval.rs:223-272) and rotating the
+ * seats over all permutations of the players (Heap's algorithm order, eval.rs:1591-1612;
+ * env e starts on permutation e % n!, the next one after each game it records).
+ * Multi-player contexts only (Connect Four, Liar's Dice, Skull; MLP, CTDE or CNN nets);
+ * CartPole returns BPPO_ERR_UNSUPPORTED.
+ *   models as in bppo_opponents_set: n_models (<= 15) parameter vectors of the context's
+ *   architecture [n_models][n_params] with optional obs normalizers (count < 2 or NULL
+ *   arrays = none); is_random [n_models] (may be NULL): 1 = the reference's None model,
+ *   all-zero logits (eval.rs:1749-1752), its parameters are not read;
+ *   seat_model [n_checkpoints] = checkpoint_to_model; n_checkpoints must equal the seated
+ *   player count (the reference's permutations cover 0..num_players only).
+ * RNG: StdRng(cfg->seed); its first u64 seeds the envs (env i = E::new(base + i), then the
+ * two resets of VecEnv::new and set_all_num_players), the sampling draws follow from word 2:
+ * per step models in ascending index, within a model its envs in ascending index, one word
+ * per draw; a move at temperature 0 draws nothing.  *rng_word_pos = the position after.
+ * games [cap] receives the recorded games in completion order (step, then env index),
+ * *n_games their count.  The loop ends at num_games games (excess envs are frozen as the
+ * reference does, eval.rs:1839-1869) or when no env is active; more than cfg->max_steps
+ * iterations is an error (one small host read per step; nothing spins without a bound).
+ * The call resets and overwrites the context's VecEnv and episode state and discards a
+ * pending pipelined rollout, like the state setters: give evaluation a context of its
+ * own with num_envs = the evaluation envs.  Parameters, optimizer, normalizers and the
+ * context's main RNG are not touched. */
+bppo_status bppo_evaluate(bppo_ctx *ctx, const bppo_eval_config *cfg, int32_t n_models, const float *params,
+                          const double *norm_mean, const double *norm_m2, const double *norm_count,
+                          const int32_t *is_random, const int32_t *seat_model, int32_t n_checkpoints,
+                          bppo_eval_game *games, int32_t cap, int32_t *n_games, uint64_t *rng_word_pos);
+
 /* parity hooks: export / import a RolloutBuffer field.  names: "obs", "priv",
  * "actions" (i32), "rewards", "dones", "values", "log_probs", "advantages",
  * "returns", "players" (i32), "all_rewards", "masks", "last_v_pp", "perm" (u32,
@@ -388,6 +442,17 @@ bppo_status bppo_debug_shuffle_engine(uint64_t seed, uint64_t stream, uint64_t s
  * non-finite log-prob (ppo.rs:363-366). */
 bppo_status bppo_debug_sample(int32_t A, int32_t B, const float *logits, const uint8_t *masks, uint64_t seed,
                               uint64_t stream, uint64_t word_pos, int32_t *actions, float *log_probs);
+
+/* evaluation parity hooks.  sample_with_temperature (eval.rs:223-272) for B host rows of A
+ * logits (A in {7, 33, 49}), masks [B*A] 0/1, one temperature per row; the rows' draws are
+ * taken in row order from word_pos of StdRng(seed) stream `stream`, one word each, rows at
+ * temperature 0 draw nothing; draws_used [B] (may be NULL) = 1 where a row drew.  device = 0
+ * runs the host build of the same source, 1 the HIP kernel. */
+bppo_status bppo_debug_eval_sample(int32_t device, int32_t A, int32_t B, const float *logits, const uint8_t *masks,
+                                   const float *temps, uint64_t seed, uint64_t stream, uint64_t word_pos,
+                                   int32_t *actions, int32_t *draws_used);
+/* generate_permutations (eval.rs:1591-1612): out [n!][n], n in 1..6 */
+bppo_status bppo_debug_eval_perms(int32_t n, int32_t *out);
 
 /* GEMM engine parity hook (host buffers).  mode 0: out[M][N] = act(A[M][K] B[K][N] + bias[N])
  * with matrixmultiply's KC=256 fma-chain order (Burn Linear forward, mlp.rs:140-206);
