@@ -4,6 +4,7 @@
     generate_permutations   eval.rs:1591-1612 (Heap's algorithm, as written)
     rewards_to_placements   eval.rs:276-306
     evaluate                eval.rs:1621-1877 run_stats_mode_env -> EvalStats (eval.rs:315-390)
+    evaluate_pods           many such matchups in one device loop, one RNG seed per pod
 
 The games run inside libbppo (bppo_evaluate, csrc/eval.hip) on a context of their
 own.  Checkpoint loading stays with bppo.checkpoint; ratings and printing are not
@@ -149,10 +150,9 @@ class EvalStats:
         return sum(1 for o in self.game_outcomes if all(p == 1 for p in o))
 
 
-def evaluate_ctx(ctx, models, normalizers, seat_model, num_games, temp_schedule, seed, max_steps=None):
-    """bppo_evaluate on an existing context (its VecEnv is reset and overwritten).
-    models[k]: a flat parameter vector, or None for the random player; normalizers[k]:
-    (mean, m2, count) or None.  -> (games as a numpy record array, rng word position)"""
+def _pack_models(ctx, models, normalizers):
+    """models[k]: a flat parameter vector or None (the random player); normalizers[k]:
+    (mean, m2, count) or None -> the arrays of bppo_evaluate / bppo_evaluate_pods"""
     K, D = len(models), ctx.obs_dim
     params = np.zeros((K, ctx.n_params), np.float32)
     is_random = np.zeros(K, np.int32)
@@ -165,15 +165,37 @@ def evaluate_ctx(ctx, models, normalizers, seat_model, num_games, temp_schedule,
         nm = normalizers[k] if normalizers else None
         if nm is not None:
             mean[k], m2[k], cnt[k] = nm
-    seats = np.ascontiguousarray(seat_model, np.int32)
+    return params, mean, m2, cnt, is_random
+
+
+def _eval_config(num_games, num_envs, temp_schedule, seed, max_steps):
     if max_steps is None:
         # every env plays at most ceil(num_games / num_envs) + 1 games; no game of these envs
         # runs longer than a few hundred moves
-        max_steps = 1000 * (num_games // max(ctx.N, 1) + 2)
-    cfg = L.EvalConfig(num_games=int(num_games), max_steps=int(max_steps), seed=int(seed),
-                       temp_initial=float(temp_schedule.initial), temp_final=float(temp_schedule.final_temp),
-                       temp_cutoff=-1 if temp_schedule.cutoff is None else int(temp_schedule.cutoff),
-                       temp_decay=int(temp_schedule.decay))
+        max_steps = 1000 * (num_games // max(num_envs, 1) + 2)
+    return L.EvalConfig(num_games=int(num_games), max_steps=int(max_steps), seed=int(seed),
+                        temp_initial=float(temp_schedule.initial), temp_final=float(temp_schedule.final_temp),
+                        temp_cutoff=-1 if temp_schedule.cutoff is None else int(temp_schedule.cutoff),
+                        temp_decay=int(temp_schedule.decay))
+
+
+def _stats(rec, pos, ncp):
+    stats = EvalStats(ncp)
+    for g in rec:
+        stats.record_with_rewards([int(x) for x in g["placement"][:ncp]], g["total_reward"][:ncp], g["length"])
+        stats.games.append((int(g["env_index"]), int(g["perm_index"]), int(g["step"])))
+    stats.rng_word_pos = pos
+    return stats
+
+
+def evaluate_ctx(ctx, models, normalizers, seat_model, num_games, temp_schedule, seed, max_steps=None):
+    """bppo_evaluate on an existing context (its VecEnv is reset and overwritten).
+    models[k]: a flat parameter vector, or None for the random player; normalizers[k]:
+    (mean, m2, count) or None.  -> (games as a numpy record array, rng word position)"""
+    K = len(models)
+    params, mean, m2, cnt, is_random = _pack_models(ctx, models, normalizers)
+    seats = np.ascontiguousarray(seat_model, np.int32)
+    cfg = _eval_config(num_games, ctx.N, temp_schedule, seed, max_steps)
     games = (L.EvalGame * max(int(num_games), 1))()
     n = C.c_int32()
     pos = C.c_uint64()
@@ -198,9 +220,54 @@ def evaluate(config, models, normalizers, seat_model, num_games, temp_schedule=N
         ncp = len(seat_model)
     finally:
         ctx.close()
-    stats = EvalStats(ncp)
-    for g in rec:
-        stats.record_with_rewards([int(x) for x in g["placement"][:ncp]], g["total_reward"][:ncp], g["length"])
-        stats.games.append((int(g["env_index"]), int(g["perm_index"]), int(g["step"])))
-    stats.rng_word_pos = pos
-    return stats
+    return _stats(rec, pos, ncp)
+
+
+def evaluate_pods_ctx(ctx, models, normalizers, pods, num_games, envs_per_pod, temp_schedule, seeds, max_steps=None):
+    """bppo_evaluate_pods on an existing context of len(pods) * envs_per_pod envs (its VecEnv
+    is reset and overwritten).  models / normalizers as in evaluate_ctx, shared by all pods;
+    pods[k]: the global model index of each checkpoint of pod k; seeds[k]: pod k's RNG seed;
+    num_games per pod.  -> [(games as a numpy record array, rng word position)] per pod,
+    each equal to evaluate_ctx alone on that pod's models with that seed"""
+    K, n_pods, cap = len(models), len(pods), max(int(num_games), 1)
+    params, mean, m2, cnt, is_random = _pack_models(ctx, models, normalizers)
+    seats = np.ascontiguousarray(pods, np.int32).reshape(n_pods, -1)
+    if seats.shape[1] != ctx.seats:
+        raise ValueError(f"every pod seats {ctx.seats} checkpoints, got {seats.shape[1]}")
+    pod_seeds = np.ascontiguousarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], np.uint64)
+    if len(pod_seeds) != n_pods:
+        raise ValueError("one seed per pod")
+    cfg = _eval_config(num_games, envs_per_pod, temp_schedule, 0, max_steps)
+    games = (L.EvalGame * (cap * n_pods))()
+    n = np.zeros(n_pods, np.int32)
+    pos = np.zeros(n_pods, np.uint64)
+    st = L.lib().bppo_evaluate_pods(ctx.h, C.byref(cfg), K, params.ctypes.data, mean.ctypes.data, m2.ctypes.data,
+                                    cnt.ctypes.data, is_random.ctypes.data, n_pods, int(envs_per_pod),
+                                    pod_seeds.ctypes.data, seats.ctypes.data, C.cast(games, C.c_void_p), cap,
+                                    n.ctypes.data, pos.ctypes.data)
+    L.check(st, ctx.h)
+    rec = np.frombuffer(games, dtype=np.dtype(L.EvalGame), count=cap * n_pods).copy().reshape(n_pods, cap)
+    return [(rec[k, :min(int(n[k]), int(num_games))], int(pos[k])) for k in range(n_pods)]
+
+
+def evaluate_pods(config, models, normalizers, pods, num_games, envs_per_pod, temp_schedule=None, seeds=None, seed=0,
+                  device=0, max_steps=None):
+    """Many matchups in one device loop (a tournament round): pod k plays num_games games
+    between models[pods[k][c]] for c in 0..P on envs_per_pod envs of a context of its own
+    with len(pods) * envs_per_pod envs.  Every pod has its own RNG, StdRng(seeds[k]) (default
+    seed + k), so pod k's EvalStats equals evaluate() alone on that pod with that seed; the
+    reference's one RNG handed from pod to pod is evaluate() pod after pod.  -> [EvalStats]"""
+    if temp_schedule is None:
+        temp_schedule = TempSchedule.env_default(config["env"])
+    pods = [tuple(int(m) for m in p) for p in pods]
+    if seeds is None:
+        seeds = [seed + k for k in range(len(pods))]
+    cfg = dict(config)
+    cfg["num_envs"] = len(pods) * int(envs_per_pod)
+    ctx = Context(cfg, device=device)
+    try:
+        out = evaluate_pods_ctx(ctx, models, normalizers, pods, num_games, envs_per_pod, temp_schedule, seeds,
+                                max_steps)
+    finally:
+        ctx.close()
+    return [_stats(rec, pos, len(pods[k])) for k, (rec, pos) in enumerate(out)]

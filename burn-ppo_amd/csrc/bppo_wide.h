@@ -38,6 +38,8 @@ struct WideStepArgs {
     // nor reset (env.rs:429-432); a finished game's totals and outcome go to sink[e]
     const uint8_t *frozen = nullptr;
     EvalOutcome *sink = nullptr;
+    // evaluation pods only: env e's seed from device memory instead of seed_base + e
+    const uint64_t *env_seed = nullptr;
 };
 
 struct SampleArgs {
@@ -81,15 +83,17 @@ struct LossArgs {
     int clip_value;
 };
 
-// players: Skull's num_players (new_with_players, main.rs:2008-2014)
+// players: Skull's num_players (new_with_players, main.rs:2008-2014); env_seed (device,
+// [N], may be null): env e's seed instead of seed_base + e (evaluation pods)
 hipError_t wide_env_reset(int kind, hipStream_t st, int N, uint64_t seed_base, int players, void *state,
-                          uint64_t *env_pos, float *ep_ret, int32_t *ep_len);
+                          uint64_t *env_pos, float *ep_ret, int32_t *ep_len, const uint64_t *env_seed = nullptr);
 // rows [priv | obs] when with_priv (CTDE), [obs] otherwise
 hipError_t wide_env_observe(int kind, int with_priv, hipStream_t st, int N, const void *state, float *xc,
                             uint8_t *mask, int32_t *players);
 hipError_t wide_env_step(int kind, hipStream_t st, const WideStepArgs &a);
 // Environment::reset of every env once more (VecEnv::set_all_num_players, env.rs:313-326)
-hipError_t wide_env_reset_again(int kind, hipStream_t st, int N, uint64_t seed_base, void *state, uint64_t *env_pos);
+hipError_t wide_env_reset_again(int kind, hipStream_t st, int N, uint64_t seed_base, void *state, uint64_t *env_pos,
+                                const uint64_t *env_seed = nullptr);
 hipError_t wide_sample(int A, hipStream_t st, const SampleArgs &g);
 hipError_t wide_boot_lvpp(hipStream_t st, int N, int P, const float *values, const int32_t *players, float *lvpp);
 hipError_t wide_gather(hipStream_t st, const uint32_t *perm, uint32_t start, uint32_t n, const float *src, int L,

@@ -112,16 +112,17 @@ __device__ __forceinline__ typename EnvT<ENV>::S *env_state(void *base) {
     return reinterpret_cast<typename EnvT<ENV>::S *>(base);
 }
 
-// VecEnv::new (env.rs:281-302): factory(seed_base + i) then reset()
+// VecEnv::new (env.rs:281-302): factory(seed_base + i) then reset().  env_seed (may be
+// null): the env's seed read from device memory instead (evaluation pods, eval.hip)
 template <int ENV>
-__global__ void k_wide_reset(int N, uint64_t seed_base, int players, void *state, uint64_t *env_pos, float *ep_ret,
-                             int32_t *ep_len) {
+__global__ void k_wide_reset(int N, uint64_t seed_base, const uint64_t *env_seed, int players, void *state,
+                             uint64_t *env_pos, float *ep_ret, int32_t *ep_len) {
     using E = EnvT<ENV>;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     typename E::S s;
     uint64_t pos = 0;
-    const Key8 k = seed_key(seed_base + (uint64_t)e);
+    const Key8 k = seed_key(env_seed ? env_seed[e] : seed_base + (uint64_t)e);
     E::reset_new(s, k, pos, players);
     env_state<ENV>(state)[e] = s;
     env_pos[e] = pos;
@@ -132,13 +133,14 @@ __global__ void k_wide_reset(int N, uint64_t seed_base, int players, void *state
 // VecEnv::set_all_num_players (env.rs:313-326): every env reset once more, from its
 // own RNG position, fixed-player games included (only set_num_players is a no-op there)
 template <int ENV>
-__global__ void k_wide_reset_again(int N, uint64_t seed_base, void *state, uint64_t *env_pos) {
+__global__ void k_wide_reset_again(int N, uint64_t seed_base, const uint64_t *env_seed, void *state,
+                                   uint64_t *env_pos) {
     using E = EnvT<ENV>;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     typename E::S s = env_state<ENV>(state)[e];
     uint64_t pos = env_pos[e];
-    E::reset(s, seed_key(seed_base + (uint64_t)e), pos);
+    E::reset(s, seed_key(env_seed ? env_seed[e] : seed_base + (uint64_t)e), pos);
     env_state<ENV>(state)[e] = s;
     env_pos[e] = pos;
 }
@@ -201,7 +203,10 @@ __global__ void k_wide_step(WideStepArgs a) {
         s = env_state<ENV>(a.state)[e];
         const int act = a.actions[e];
         const int p_act = E::player(s);
-        k = seed_key(a.seed_base + (uint64_t)e);
+        uint64_t seed = a.seed_base + (uint64_t)e;
+        if constexpr (EVAL)
+            if (a.env_seed) seed = a.env_seed[e];
+        k = seed_key(seed);
         pos = a.env_pos[e];
         float r[BPPO_MAX_PLAYERS] = {0, 0, 0, 0, 0, 0};
         int bad = 0;
@@ -504,9 +509,9 @@ __global__ void __launch_bounds__(64) k_wide_metric_reduce(const double *part, i
     } while (0)
 
 hipError_t wide_env_reset(int kind, hipStream_t st, int N, uint64_t seed_base, int players, void *state,
-                          uint64_t *env_pos, float *ep_ret, int32_t *ep_len) {
-    ENV_DISPATCH(kind, k_wide_reset, dim3((N + 255) / 256), dim3(256), N, seed_base, players, state, env_pos, ep_ret,
-                 ep_len);
+                          uint64_t *env_pos, float *ep_ret, int32_t *ep_len, const uint64_t *env_seed) {
+    ENV_DISPATCH(kind, k_wide_reset, dim3((N + 255) / 256), dim3(256), N, seed_base, env_seed, players, state, env_pos,
+                 ep_ret, ep_len);
     return hipGetLastError();
 }
 
@@ -547,8 +552,9 @@ hipError_t wide_env_step(int kind, hipStream_t st, const WideStepArgs &a) {
     return hipGetLastError();
 }
 
-hipError_t wide_env_reset_again(int kind, hipStream_t st, int N, uint64_t seed_base, void *state, uint64_t *env_pos) {
-    ENV_DISPATCH(kind, k_wide_reset_again, dim3((N + 255) / 256), dim3(256), N, seed_base, state, env_pos);
+hipError_t wide_env_reset_again(int kind, hipStream_t st, int N, uint64_t seed_base, void *state, uint64_t *env_pos,
+                                const uint64_t *env_seed) {
+    ENV_DISPATCH(kind, k_wide_reset_again, dim3((N + 255) / 256), dim3(256), N, seed_base, env_seed, state, env_pos);
     return hipGetLastError();
 }
 

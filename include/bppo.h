@@ -332,6 +332,43 @@ bppo_status bppo_evaluate(bppo_ctx *ctx, const bppo_eval_config *cfg, int32_t n_
                           const int32_t *is_random, const int32_t *seat_model, int32_t n_checkpoints,
                           bppo_eval_game *games, int32_t cap, int32_t *n_games, uint64_t *rng_word_pos);
 
+/* Many evaluation matchups ("pods") in one loop: a tournament round.  Pod k owns envs
+ * [k E, (k + 1) E), E = envs_per_pod; the context's num_envs must equal n_pods * E.  Only the
+ * forward pass is shared: the rows one model moves in every pod go through one GEMM group.
+ * Multi-player contexts only; CartPole returns BPPO_ERR_UNSUPPORTED.
+ *   models as in bppo_evaluate with n_models 1..64; n_pods 1..1024; cfg->seed is ignored;
+ *   pod_seeds [n_pods]; pod_seat_model [n_pods][P], P = the seated player count: within pod k
+ *   checkpoint c is played by global model pod_seat_model[k][c].  A model's local slot in a
+ *   pod is the rank of its first appearance in pod_seat_model[k][0..P) (run_pod's
+ *   de-duplication, tournament.rs:1811-1838): seats [3, 1, 3] give local models [m3, m1]
+ *   and the local seat map [0, 1, 0].
+ * Pod k equals, in every recorded field and in its final word position, bppo_evaluate alone
+ * on a context of E envs with cfg->seed = pod_seeds[k], the pod's local models in local-slot
+ * order and the local seat map:
+ *   RNG StdRng(pod_seeds[k]); its first u64 seeds the pod's envs (env j of the pod =
+ *   E::new(base_k + j), then the two resets); draws follow from word 2, per step over the
+ *   pod's models in ascending local slot, within a model over the pod's envs in ascending
+ *   index, one word per draw, none at temperature 0;
+ *   the permutation rotation starts at j % n!; the num_games cap and the freeze rule
+ *   (eval.rs:1839-1869) apply per pod;
+ *   games [n_pods][cap_per_pod]: pod k's games in completion order (step, then env) at
+ *   games[k * cap_per_pod ...], env_index the index within the pod, step the shared loop
+ *   iteration (all pods start at iteration 0, so it is the single call's);
+ *   n_games [n_pods], rng_word_pos [n_pods] (may be NULL).
+ * This departs from the reference, which hands one StdRng from pod to pod (pod k + 1 starts
+ * where pod k ended, tournament.rs:2151-2184); that order is bppo_evaluate pod after pod.
+ * The loop ends when every pod has num_games games or no active env; a finished pod's envs
+ * are frozen.  A pod unfinished after cfg->max_steps iterations: BPPO_ERR_ARG ("max_steps").
+ * BPPO_ERR_ARG with a message, before any launch: NULL pod_seeds, pod_seat_model or n_games;
+ * n_pods * envs_per_pod != num_envs; a seat naming a model outside [0, n_models); n_models
+ * outside 1..64; n_pods outside 1..1024; missing params when some model is not random.
+ * Side effects on the context as for bppo_evaluate. */
+bppo_status bppo_evaluate_pods(bppo_ctx *ctx, const bppo_eval_config *cfg, int32_t n_models, const float *params,
+                               const double *norm_mean, const double *norm_m2, const double *norm_count,
+                               const int32_t *is_random, int32_t n_pods, int32_t envs_per_pod,
+                               const uint64_t *pod_seeds, const int32_t *pod_seat_model, bppo_eval_game *games,
+                               int32_t cap_per_pod, int32_t *n_games, uint64_t *rng_word_pos);
+
 /* parity hooks: export / import a RolloutBuffer field.  names: "obs", "priv",
  * "actions" (i32), "rewards", "dones", "values", "log_probs", "advantages",
  * "returns", "players" (i32), "all_rewards", "masks", "last_v_pp", "perm" (u32,
