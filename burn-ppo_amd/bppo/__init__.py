@@ -8,3 +8,5 @@ from .tournament import round_robin_pods, run_round, swiss_points  # noqa: F401
 from .host import make_config, minibatch_sizes, orthogonal_init, schedule_get  # noqa: F401
 from .ppo import (ActorCritic, Context, RolloutBuffer, Trainer, VecEnv, collect_rollouts,  # noqa: F401
                   compute_gae, perf_scalars, ppo_update, rollout_episodes, train_step)
+from .pool import OpponentPool, OpponentStats, PoolTrainer  # noqa: F401
+from .rng import StdRng  # noqa: F401

@@ -65,6 +65,13 @@ class EvalGame(C.Structure):
                 ("length", C.c_int32), ("env_index", C.c_int32), ("perm_index", C.c_int32), ("step", C.c_int32)]
 
 
+class OppCompletion(C.Structure):
+    """bppo_opp_completion: one finished opponent-pool game with the seats it was played under"""
+    _fields_ = [("env_index", C.c_int32), ("step", C.c_int32), ("learner_position", C.c_int32),
+                ("n_players", C.c_int32), ("placement", C.c_int32 * MAX_PLAYERS),
+                ("position_to_opponent", C.c_int32 * MAX_PLAYERS)]
+
+
 METRIC_NAMES = ("policy_loss", "value_loss", "entropy", "entropy_scaled", "approx_kl", "clip_fraction",
                 "explained_variance", "total_loss", "value_mean", "returns_mean", "adv_mean_raw",
                 "adv_std_raw", "adv_min_raw", "adv_max_raw", "value_error_mean", "value_error_std",
@@ -100,12 +107,14 @@ EXPORTS = (
     "bppo_debug_record_params",
     "bppo_evaluate", "bppo_eval_config_size", "bppo_eval_game_size", "bppo_debug_eval_sample",
     "bppo_debug_eval_perms", "bppo_evaluate_pods",
+    "bppo_opp_completion_size", "bppo_opponents_completions", "bppo_opponents_results",
 )
 
 # ABI struct -> the library's sizeof export (checked when the library loads)
 STRUCT_SIZES = {"bppo_config_size": Config, "bppo_update_metrics_size": UpdateMetrics,
                 "bppo_episode_size": Episode, "bppo_rollout_info_size": RolloutInfo,
-                "bppo_eval_config_size": EvalConfig, "bppo_eval_game_size": EvalGame}
+                "bppo_eval_config_size": EvalConfig, "bppo_eval_game_size": EvalGame,
+                "bppo_opp_completion_size": OppCompletion}
 
 _lib = None
 
@@ -161,6 +170,8 @@ def lib():
         "bppo_get_stream": (i32, [vp, C.POINTER(vp)]),
         "bppo_opponents_set": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp]),
         "bppo_opponents_get_envs": (i32, [vp, vp, vp]),
+        "bppo_opponents_completions": (i32, [vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]),
+        "bppo_opponents_results": (i32, [vp, vp, vp, vp]),
         "bppo_buffer_get": (i32, [vp, C.c_char_p, vp, sz]),
         "bppo_buffer_set": (i32, [vp, C.c_char_p, vp, sz]),
         "bppo_gae_device": (i32, [vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]),

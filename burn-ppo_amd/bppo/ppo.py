@@ -158,6 +158,7 @@ class Context:
                                              cnt.ctypes.data, int(num_opponent_envs), lp.ctypes.data,
                                              po.ctypes.data, co.ctypes.data))
         self._n_opp = int(num_opponent_envs)
+        self._n_models = int(K)
 
     def opponent_envs(self):
         """-> (learner_pos [n_opp], pos_to_opp [n_opp, P]) after the last rollout"""
@@ -165,6 +166,34 @@ class Context:
         lp = np.zeros(max(n, 1), np.int32); po = np.zeros(max(n, 1) * self.seats, np.int32)
         self._chk(L.lib().bppo_opponents_get_envs(self.h, lp.ctypes.data, po.ctypes.data))
         return lp[:n], po[:n * self.seats].reshape(n, self.seats)
+
+    def opponent_completions(self, cap=None):
+        """opponent_completions of the last rollout (ppo.rs:505-521, 871-917) in (step, env)
+        order -> (list of dicts, dropped).  Each game carries the seats it was played under:
+        placements [P] (1 = first), learner_position, position_to_opponent [P] (device model
+        slot, -1 on the learner's seat).  cap: at most that many records (the first ones)."""
+        n, dropped = C.c_int32(), C.c_int32()
+        self._chk(L.lib().bppo_opponents_completions(self.h, None, 0, C.byref(n), C.byref(dropped)))
+        m = n.value if cap is None else min(int(cap), n.value)
+        recs = (L.OppCompletion * max(m, 1))()
+        if m > 0:
+            self._chk(L.lib().bppo_opponents_completions(self.h, recs, m, C.byref(n), C.byref(dropped)))
+        out = []
+        for i in range(m):
+            r = recs[i]
+            P = r.n_players
+            out.append(dict(env_index=r.env_index, step=r.step, learner_position=r.learner_position,
+                            placements=list(r.placement[:P]), position_to_opponent=list(r.position_to_opponent[:P])))
+        return out, dropped.value
+
+    def opponent_results(self):
+        """OpponentPool::queue_game_result summed over the last rollout's finished opponent
+        games, per device model slot -> (wins, games, swiss_points), integer arrays [K]"""
+        K = getattr(self, "_n_models", 0)
+        wins = np.zeros(max(K, 1), np.int32); games = np.zeros(max(K, 1), np.int32)
+        swiss = np.zeros(max(K, 1), np.int64)
+        self._chk(L.lib().bppo_opponents_results(self.h, wins.ctypes.data, games.ctypes.data, swiss.ctypes.data))
+        return wins[:K], games[:K], swiss[:K]
 
     def kernel_ms(self, name):
         f = C.c_float()

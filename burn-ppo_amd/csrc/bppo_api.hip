@@ -434,6 +434,7 @@ void drop_prefetch(bppo_ctx *c) {   // (also eval.hip)
     c->prefetched = false;
     c->collected = 0;
     c->gae_done = 0;
+    (void)opp_records_clear(c);   // its finished opponent games go with it
 }
 
 extern "C" bppo_status bppo_params_set(bppo_ctx *c, const float *h, size_t n) {
@@ -774,6 +775,7 @@ static bppo_status collect_enqueue(bppo_ctx *c, bool summary) {
     if (c->wide) {
         BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
         BPPO_HIP(c, hipMemsetAsync(c->d_err, 0, 4, c->stream));
+        if (opp_active(c)) TRY(opp_records_clear(c));   // the finished opponent games go with the episodes
     }
     const uint64_t base = c->rng_pos;
     TRY(tm_begin(c, tro));

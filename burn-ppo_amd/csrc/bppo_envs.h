@@ -650,18 +650,18 @@ __device__ __forceinline__ void sk_priv(const SKState &s, float *g) {
 // connect_four.rs:301-310.  The state keeps no winner: a win leaves `cur` on the
 // winner (c4_step does not switch it), and a full board without a win leaves it
 // on the last mover, who then has no line of four.
+// A line of four from cell bit b = 7 r + c steps by 1 (row), 7 (column), 8 or 6 (diagonals):
+// four shifted copies of the plane ANDed leave the lines' first cells.  Rows are 7 bits
+// with no gap, so a row or down-right line must start in columns 0-3 and a down-left
+// line in columns 3-6, or it would wrap into the next row; bits past 41 are 0, which
+// bounds the rows.  (The rollout of an opponent pool runs this for every finished game.)
 __device__ __forceinline__ bool c4_has_four(uint64_t m) {
-    const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1};
-    for (int r = 0; r < 6; r++)
-        for (int c = 0; c < 7; c++)
-            for (int d = 0; d < 4; d++) {
-                const int r3 = r + 3 * dr[d], c3 = c + 3 * dc[d];
-                if (r3 >= 6 || c3 < 0 || c3 >= 7) continue;
-                bool all = true;
-                for (int i = 0; i < 4; i++) all = all && ((m >> ((r + i * dr[d]) * 7 + c + i * dc[d])) & 1ull);
-                if (all) return true;
-            }
-    return false;
+    constexpr uint64_t COLS_0_3 = 0x78f1e3c78full, COLS_3_6 = 0x3c78f1e3c78ull;
+    const uint64_t h = m & (m >> 1) & (m >> 2) & (m >> 3);
+    const uint64_t v = m & (m >> 7) & (m >> 14) & (m >> 21);
+    const uint64_t d = m & (m >> 8) & (m >> 16) & (m >> 24);
+    const uint64_t a = m & (m >> 6) & (m >> 12) & (m >> 18);
+    return ((h & COLS_0_3) | v | (d & COLS_0_3) | (a & COLS_3_6)) != 0;
 }
 __device__ __forceinline__ bool c4_outcome(const C4State &s, int32_t out[6]) {
     for (int p = 0; p < 6; p++) out[p] = 0;

@@ -62,6 +62,16 @@ struct EpisodeRec {
     int32_t length, env_index, step, pad;
 };
 
+// opponent-pool rollouts (opponents.hip): the rollout's finished-game count and the sums of
+// OpponentPool::queue_game_result per device model slot (opponent_pool.rs:578-616)
+constexpr int OPP_MAX_MODELS = 15;
+struct OppResults {
+    int32_t count;                       // finished opponent games with an outcome (kept or not)
+    int32_t pad;
+    int32_t wins[OPP_MAX_MODELS], games[OPP_MAX_MODELS];
+    unsigned long long swiss[OPP_MAX_MODELS];
+};
+
 // Welford state (count, mean, M2) — Chan merge is the associative combine
 struct Welford { double n, mean, m2; };
 
@@ -366,6 +376,10 @@ struct bppo_ctx {
     uint32_t *d_nvalid = nullptr;
     uint32_t n_valid = 0;
     int32_t *d_gbase = nullptr, *h_gbase = nullptr;   // per step: draw-order base of each mover group
+    // finished opponent games of the rollout d_eps describes (bppo_opponents_completions / _results)
+    uint32_t *d_opp_out = nullptr;    // [N] the step's packed game_outcome per env (opp_pack_outcome)
+    bppo_opp_completion *d_comp = nullptr;   // [eps_cap] records in (step, env) order
+    bppo::OppResults *d_opp_res = nullptr;
     double *d_obsw_part = nullptr;    // normalize_obs: per-chunk partial stats [256][D][3]
     size_t obsw_part_n = 0;
     uint8_t *d_mask = nullptr;        // action masks [T][N][A] (0/1)
@@ -532,6 +546,7 @@ bool opp_active(const bppo_ctx *c);
 bppo_status opp_alloc(bppo_ctx *c);
 void opp_free(bppo_ctx *c);
 bppo_status opp_rollout_begin(bppo_ctx *c, uint64_t base);
+bppo_status opp_records_clear(bppo_ctx *c);   // no finished games, zero sums (stream-ordered)
 bppo_status opp_step_group(bppo_ctx *c, int t);
 bppo_status opp_step_forwards(bppo_ctx *c);
 bppo_status opp_step_seats(bppo_ctx *c, int t);

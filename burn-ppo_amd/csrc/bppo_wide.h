@@ -40,7 +40,20 @@ struct WideStepArgs {
     EvalOutcome *sink = nullptr;
     // evaluation pods only: env e's seed from device memory instead of seed_base + e
     const uint64_t *env_seed = nullptr;
+    // opponent-pool rollouts only (null otherwise): a finished game of an env in [0, n_opp)
+    // leaves its game_outcome here before the reset, packed by opp_pack_outcome; k_opp_seats
+    // reads it the same step (ppo.rs:871-917)
+    uint32_t *opp_out = nullptr;
+    int n_opp = 0;
 };
+
+// Environment::game_outcome of one finished game in one word: placement of seat p (1 = first,
+// 0 beyond the seated players) in bits [4p, 4p + 4), bit 24 = the env reported an outcome
+__host__ __device__ inline uint32_t opp_pack_outcome(bool has, const int32_t placement[6]) {
+    uint32_t v = has ? 1u << 24 : 0u;
+    for (int p = 0; p < 6; p++) v |= ((uint32_t)placement[p] & 15u) << (4 * p);
+    return v;
+}
 
 struct SampleArgs {
     int N, P;

@@ -186,8 +186,10 @@ __global__ void __launch_bounds__(64) k_wide_observe(int N, const void *state, f
 // and auto-reset.  EVAL (eval.hip, run_stats_mode_env): an env marked terminal is
 // skipped entirely (env.rs:429-432) -- its lane still joins wave_episode_slot, not
 // done -- and a finished game's totals and game_outcome go to the sink before the
-// reset (env.rs:442-450).  The training launches instantiate EVAL = false.
-template <int ENV, bool EVAL>
+// reset (env.rs:442-450).  The training launches instantiate EVAL = false.  OPP (opponent-pool
+// rollouts, opponents.hip): a finished game of an env in [0, n_opp) leaves its game_outcome
+// in opp_out[e] before the reset (ppo.rs:871-877); nothing else differs from the training code.
+template <int ENV, bool EVAL, bool OPP = false>
 __global__ void k_wide_step(WideStepArgs a) {
     using E = EnvT<ENV>;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -233,6 +235,13 @@ __global__ void k_wide_step(WideStepArgs a) {
             o.length = len;
             o.has_outcome = E::outcome(s, o.placement) ? 1 : 0;
             a.sink[e] = o;
+        }
+        if constexpr (OPP) {
+            if (e < a.n_opp) {
+                int32_t pl[6];
+                const bool has = E::outcome(s, pl);
+                a.opp_out[e] = opp_pack_outcome(has, pl);
+            }
         }
         if (slot < a.eps_cap) {
             EpisodeRec rec;
@@ -536,17 +545,21 @@ hipError_t wide_env_observe(int kind, int with_priv, hipStream_t st, int N, cons
 hipError_t wide_env_step(int kind, hipStream_t st, const WideStepArgs &a) {
     const dim3 grid((a.N + 255) / 256), block(256);
     const bool ev = a.frozen != nullptr && a.sink != nullptr;
+    const bool op = !ev && a.opp_out != nullptr && a.n_opp > 0;
     if (kind == BPPO_ENV_CONNECT_FOUR) {
         if (ev) hipLaunchKernelGGL((k_wide_step<BPPO_ENV_CONNECT_FOUR, true>), grid, block, 0, st, a);
+        else if (op) hipLaunchKernelGGL((k_wide_step<BPPO_ENV_CONNECT_FOUR, false, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((k_wide_step<BPPO_ENV_CONNECT_FOUR, false>), grid, block, 0, st, a);
     } else if (kind == BPPO_ENV_CARTPOLE) {
         if (ev) return hipErrorInvalidValue;     // no stats mode for CartPole
         hipLaunchKernelGGL((k_wide_step<BPPO_ENV_CARTPOLE, false>), grid, block, 0, st, a);
     } else if (kind == BPPO_ENV_SKULL) {
         if (ev) hipLaunchKernelGGL((k_wide_step<BPPO_ENV_SKULL, true>), grid, block, 0, st, a);
+        else if (op) hipLaunchKernelGGL((k_wide_step<BPPO_ENV_SKULL, false, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((k_wide_step<BPPO_ENV_SKULL, false>), grid, block, 0, st, a);
     } else {
         if (ev) hipLaunchKernelGGL((k_wide_step<BPPO_ENV_LIARS_DICE, true>), grid, block, 0, st, a);
+        else if (op) hipLaunchKernelGGL((k_wide_step<BPPO_ENV_LIARS_DICE, false, true>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((k_wide_step<BPPO_ENV_LIARS_DICE, false>), grid, block, 0, st, a);
     }
     return hipGetLastError();

@@ -13,7 +13,9 @@
 //   its own normalized copy, its rows' logits selected into the step's logits
 //   sampling (k_sample_masked) at word base + position * A
 //   env step, then k_opp_seats: the step's N*A Gumbel words, then for every
-//   finished opponent game in env order OpponentPool::sample_all_slots and
+//   finished opponent game in env order its OpponentEpisodeCompletion record and
+//   queue_game_result sums (ppo.rs:871-917, opponent_pool.rs:578-616) from the seats
+//   it was played under, then OpponentPool::sample_all_slots and
 //   EnvState::shuffle_positions from the main RNG (usize gen_range + u32
 //   shuffle), then the learner-turn flags against the reshuffled seats.
 // The main RNG position therefore lives on the device during the rollout and
@@ -26,7 +28,6 @@
 
 namespace bppo {
 
-constexpr int OPP_MAX_MODELS = 15;
 constexpr int OG_THREADS = 1024;
 
 __global__ void k_set_u64(uint64_t *p, uint64_t v) { *p = v; }
@@ -138,37 +139,111 @@ __device__ __forceinline__ uint32_t dev_range_u32(Cur &c, uint32_t range) {
 // every finished opponent game (env order, main RNG), then the learner-turn
 // flags against the new seats (ppo.rs:874-925, 928-937)
 constexpr int SEAT_THREADS = 1024, SEAT_CHUNK = 8192, SEAT_WORDS = 4096, SEAT_MARGIN = 64;
+constexpr int SEAT_PER = SEAT_CHUNK / SEAT_THREADS;   // envs per thread and chunk, at most
+static_assert(SEAT_CHUNK < (1 << 16), "a chunk's two counts share one word");
+// the OpponentEpisodeCompletion records of one thread's envs [e0, e0 + SEAT_PER) of a chunk, from
+// registers: oc = the env's outcome word (opp_pack_outcome), snap = bit 31 a record is due,
+// bits [24, 27) the learner's seat, 4 bits per seat the model slot (15 = none) -- the seats
+// as they were before the reshuffle.  Slots from `orec` on; past `cap` nothing is written
+__device__ __forceinline__ void seat_write_records(const uint32_t (&oc)[SEAT_PER], const uint32_t (&snap)[SEAT_PER],
+                                                   int e0, int orec, int t, int P, bppo_opp_completion *comp,
+                                                   int cap) {
+#pragma unroll
+    for (int i = 0; i < SEAT_PER; i++) {
+        if (!(snap[i] >> 31)) continue;
+        bppo_opp_completion rec;
+        rec.env_index = e0 + i; rec.step = t; rec.learner_position = (int)((snap[i] >> 24) & 7u); rec.n_players = P;
+#pragma unroll
+        for (int p = 0; p < BPPO_MAX_PLAYERS; p++) {
+            const int m = (int)((snap[i] >> (4 * p)) & 15u);
+            rec.placement[p] = p < P ? (int)((oc[i] >> (4 * p)) & 15u) : 0;
+            rec.position_to_opponent[p] = (p < P && m != 15) ? m : -1;
+        }
+        if (orec < cap) comp[orec] = rec;
+        orec++;
+    }
+}
+
 __global__ void __launch_bounds__(SEAT_THREADS) k_opp_seats(int N, int n_opp, int P, int A, const float *done,
                                                             const int32_t *players, Key8 key, uint64_t stream,
                                                             const int32_t *curopp, uint64_t *rngpos, int32_t *lpos,
-                                                            int32_t *p2o, float *valid) {
+                                                            int32_t *p2o, float *valid, int t, const uint32_t *outcome,
+                                                            bppo_opp_completion *comp, int comp_cap, OppResults *res) {
     __shared__ int list[SEAT_CHUNK];
-    __shared__ int cnt[SEAT_THREADS];
+    __shared__ int cnt[SEAT_THREADS];           // finished games | those with an outcome << 16
     __shared__ uint32_t words[SEAT_WORDS];
     __shared__ uint64_t pos;
     __shared__ int qnext;
+    __shared__ int rec_base, rec_chunk;         // the rollout's records so far; before this chunk
+    __shared__ int s_wins[OPP_MAX_MODELS], s_games[OPP_MAX_MODELS], s_swiss[OPP_MAX_MODELS];
     const int tid = threadIdx.x;
-    if (tid == 0) pos = *rngpos + (uint64_t)N * A;
+    if (tid == 0) { pos = *rngpos + (uint64_t)N * A; rec_base = res->count; }
+    if (tid < OPP_MAX_MODELS) { s_wins[tid] = 0; s_games[tid] = 0; s_swiss[tid] = 0; }
     // finished opponent games in env order, chunk by chunk: flags read in
     // parallel and compacted, the draws (sequential in the RNG) on one thread
+    float dn[SEAT_PER];
+    uint32_t oc[SEAT_PER], snap[SEAT_PER];
+    int e0 = 0, orec0 = 0;
     for (int c0 = 0; c0 < n_opp; c0 += SEAT_CHUNK) {
         const int c1 = min(n_opp, c0 + SEAT_CHUNK);
         const int per = (c1 - c0 + SEAT_THREADS - 1) / SEAT_THREADS;
-        const int e0 = c0 + tid * per, e1 = min(c1, e0 + per);
+        e0 = c0 + tid * per;
+        const int e1 = min(c1, e0 + per);
+        // the thread's done flags and outcome words, loaded once (clamped, none conditional)
+#pragma unroll
+        for (int i = 0; i < SEAT_PER; i++) {
+            const int e = min(e0 + i, n_opp - 1);
+            dn[i] = done[e];
+            oc[i] = outcome[e];
+        }
         int k = 0;
-        for (int e = e0; e < e1; e++) k += done[e] != 0.0f;
+#pragma unroll
+        for (int i = 0; i < SEAT_PER; i++) {
+            if (i >= per || e0 + i >= e1) dn[i] = 0.0f;
+            if (dn[i] != 0.0f) k += 1 + (int)(((oc[i] >> 24) & 1u) << 16);
+        }
         cnt[tid] = k;
         __syncthreads();
         if (tid == 0) {
             int run = 0;
             for (int q = 0; q < SEAT_THREADS; q++) { const int v = cnt[q]; cnt[q] = run; run += v; }
-            list[SEAT_CHUNK - 1] = run;   // count (list slot reused after the writes below)
+            list[SEAT_CHUNK - 1] = run & 0xffff;   // count (list slot reused after the writes below)
+            rec_chunk = rec_base;
+            rec_base += run >> 16;
         }
         __syncthreads();
         const int nd = list[SEAT_CHUNK - 1];
         __syncthreads();
-        int o = cnt[tid];
-        for (int e = e0; e < e1; e++) if (done[e] != 0.0f) list[o++] = e;
+        // the chunk's finished games compacted in env order.  Each with an outcome adds its
+        // queue_game_result terms (opponent_pool.rs:591-614) and keeps the seats it was played
+        // under in a register: the barrier below stands between these reads of lpos / p2o and
+        // the reshuffle that overwrites them.  Its record (slot = its rank in (step, env)
+        // order) is stored once the draws are done, so no store is waited for on their way
+        int o = cnt[tid] & 0xffff;
+        orec0 = rec_chunk + (cnt[tid] >> 16);
+#pragma unroll
+        for (int i = 0; i < SEAT_PER; i++) {
+            snap[i] = 0;
+            if (dn[i] == 0.0f) continue;
+            const int e = e0 + i;
+            list[o++] = e;
+            const uint32_t w = oc[i];
+            if (!((w >> 24) & 1)) continue;        // no game_outcome: no record, still reshuffled (ppo.rs:877-916)
+            const int lp = lpos[e];
+            const int lplace = (int)((w >> (4 * lp)) & 15u);
+            uint32_t sn = (1u << 31) | ((uint32_t)lp << 24);
+            for (int p = 0; p < P; p++) {
+                const int m = p2o[(size_t)e * P + p];
+                const bool opp = p != lp && m >= 0 && m < OPP_MAX_MODELS;
+                sn |= (opp ? (uint32_t)m : 15u) << (4 * p);
+                if (opp) {
+                    atomicAdd(&s_games[m], 1);
+                    atomicAdd(&s_swiss[m], P - lplace);
+                    if (lplace < (int)((w >> (4 * p)) & 15u)) atomicAdd(&s_wins[m], 1);
+                }
+            }
+            snap[i] = sn;
+        }
         __syncthreads();
         if (tid == 0) qnext = 0;
         __syncthreads();
@@ -199,10 +274,18 @@ __global__ void __launch_bounds__(SEAT_THREADS) k_opp_seats(int N, int n_opp, in
             }
             __syncthreads();
         }
+        // (the last chunk's records go out at the kernel's end, beside the valid flags)
+        if (c0 + SEAT_CHUNK < n_opp) seat_write_records(oc, snap, e0, orec0, t, P, comp, comp_cap);
     }
-    if (tid == 0) *rngpos = pos;
+    if (tid == 0) { *rngpos = pos; res->count = rec_base; }
     __threadfence_block();
     __syncthreads();
+    if (n_opp > 0) seat_write_records(oc, snap, e0, orec0, t, P, comp, comp_cap);
+    if (tid < OPP_MAX_MODELS && s_games[tid] != 0) {      // the launch's sums, flushed once
+        atomicAdd(&res->wins[tid], s_wins[tid]);
+        atomicAdd(&res->games[tid], s_games[tid]);
+        atomicAdd(&res->swiss[tid], (unsigned long long)s_swiss[tid]);
+    }
     for (int e = tid; e < N; e += blockDim.x)
         valid[e] = (e >= n_opp || players[e] == lpos[e]) ? 1.0f : 0.0f;
 }
@@ -240,13 +323,14 @@ bool opp_active(const bppo_ctx *c) { return c->wide && c->n_opp > 0 && c->opp_K 
 void opp_free(bppo_ctx *c) {
     void *ptrs[] = {c->d_opp_params, c->d_opp_on, c->d_lpos, c->d_p2o, c->d_curopp, c->d_group, c->d_gpos,
                     c->d_valid, c->d_rngpos, c->d_oraw, c->d_oxc, c->d_ologits, c->d_vidx, c->d_Jopp, c->d_nvalid,
-                    c->d_gbase};
+                    c->d_gbase, c->d_opp_out, c->d_comp, c->d_opp_res};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->h_gbase) (void)hipHostFree(c->h_gbase);
     c->h_gbase = nullptr; c->d_gbase = nullptr;
     c->d_opp_params = nullptr; c->d_opp_on = nullptr; c->d_lpos = c->d_p2o = c->d_curopp = nullptr;
     c->d_group = c->d_gpos = nullptr; c->d_valid = nullptr; c->d_rngpos = nullptr;
     c->d_oraw = c->d_oxc = c->d_ologits = nullptr; c->d_vidx = c->d_Jopp = c->d_nvalid = nullptr;
+    c->d_opp_out = nullptr; c->d_comp = nullptr; c->d_opp_res = nullptr;
 }
 
 template <class T>
@@ -272,6 +356,15 @@ bppo_status opp_alloc(bppo_ctx *c) {
     TRY(oalloc(c, &c->d_curopp, 4));
     TRY(oalloc(c, &c->d_gbase, OPP_MAX_MODELS + 2));
     if (!c->h_gbase) BPPO_HIP(c, hipHostMalloc((void **)&c->h_gbase, sizeof(int32_t) * (OPP_MAX_MODELS + 2)));
+    TRY(oalloc(c, &c->d_opp_out, N));
+    TRY(oalloc(c, &c->d_comp, (size_t)c->eps_cap));
+    TRY(oalloc(c, &c->d_opp_res, 1));
+    return BPPO_OK;
+}
+
+// the records and sums describe one rollout: emptied where the episode counter is
+bppo_status opp_records_clear(bppo_ctx *c) {
+    if (c->d_opp_res) BPPO_HIP(c, hipMemsetAsync(c->d_opp_res, 0, sizeof(OppResults), c->stream));
     return BPPO_OK;
 }
 
@@ -334,7 +427,7 @@ bppo_status opp_step_seats(bppo_ctx *c, int t) {
     const size_t r0 = (size_t)t * c->N;
     hipLaunchKernelGGL(k_opp_seats, dim3(1), dim3(SEAT_THREADS), 0, c->stream, c->N, c->n_opp, c->Pa, c->A, c->d_done + r0,
                        c->d_players + r0, c->rng_key, (uint64_t)c->cfg.rng_stream, c->d_curopp, c->d_rngpos,
-                       c->d_lpos, c->d_p2o, c->d_valid + r0);
+                       c->d_lpos, c->d_p2o, c->d_valid + r0, t, c->d_opp_out, c->d_comp, (int)c->eps_cap, c->d_opp_res);
     TRY(launch_check(c, __func__));
     return BPPO_OK;
 }
@@ -399,6 +492,9 @@ extern "C" bppo_status bppo_opponents_set(bppo_ctx *c, int32_t n_models, const f
             if (current_opp[i] < 0 || current_opp[i] >= n_models) { c->err = "opponent pool: current_opp out of range"; return BPPO_ERR_ARG; }
     }
     TRY(opp_alloc(c));
+    // the finished games on record were played under the seats and models replaced here
+    TRY(opp_records_clear(c));
+    BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
     if (c->d_opp_params) { (void)hipFree(c->d_opp_params); c->d_opp_params = nullptr; }
     if (c->d_opp_on) { (void)hipFree(c->d_opp_on); c->d_opp_on = nullptr; }
     if (c->d_lpos) { (void)hipFree(c->d_lpos); c->d_lpos = nullptr; }
@@ -441,5 +537,41 @@ extern "C" bppo_status bppo_opponents_get_envs(bppo_ctx *c, int32_t *learner_pos
     if (pos_to_opp)
         BPPO_HIP(c, hipMemcpyAsync(pos_to_opp, c->d_p2o, sizeof(int32_t) * (size_t)c->n_opp * c->Pa, hipMemcpyDeviceToHost, c->stream));
     BPPO_HIP(c, hipStreamSynchronize(c->stream));
+    return BPPO_OK;
+}
+
+extern "C" size_t bppo_opp_completion_size(void) { return sizeof(bppo_opp_completion); }
+
+// ppo.rs:505-521, 871-917: see include/bppo.h
+extern "C" bppo_status bppo_opponents_completions(bppo_ctx *c, bppo_opp_completion *out, int32_t cap, int32_t *n,
+                                                  int32_t *dropped) {
+    if (!c) return BPPO_ERR_ARG;
+    if (!opp_active(c)) { c->err = "opponents_completions: no opponents set"; return BPPO_ERR_ARG; }
+    if (cap < 0 || (cap > 0 && !out)) { c->err = "opponents_completions: cap < 0 or no output array"; return BPPO_ERR_ARG; }
+    OppResults r;
+    BPPO_HIP(c, hipMemcpyAsync(&r, c->d_opp_res, sizeof r, hipMemcpyDeviceToHost, c->stream));
+    BPPO_HIP(c, hipStreamSynchronize(c->stream));
+    const int kept = std::min(r.count, c->eps_cap), m = std::min(kept, cap);
+    if (m > 0) {
+        BPPO_HIP(c, hipMemcpyAsync(out, c->d_comp, sizeof(bppo_opp_completion) * (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        BPPO_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    if (n) *n = kept;
+    if (dropped) *dropped = r.count - kept;
+    return BPPO_OK;
+}
+
+// opponent_pool.rs:578-616: see include/bppo.h
+extern "C" bppo_status bppo_opponents_results(bppo_ctx *c, int32_t *wins, int32_t *games, int64_t *swiss_points) {
+    if (!c) return BPPO_ERR_ARG;
+    if (!opp_active(c)) { c->err = "opponents_results: no opponents set"; return BPPO_ERR_ARG; }
+    OppResults r;
+    BPPO_HIP(c, hipMemcpyAsync(&r, c->d_opp_res, sizeof r, hipMemcpyDeviceToHost, c->stream));
+    BPPO_HIP(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < c->opp_K; k++) {
+        if (wins) wins[k] = r.wins[k];
+        if (games) games[k] = r.games[k];
+        if (swiss_points) swiss_points[k] = (int64_t)r.swiss[k];
+    }
     return BPPO_OK;
 }

@@ -233,6 +233,7 @@ bppo_status wide_collect(bppo_ctx *c, uint64_t base) {
         w.all_r = c->d_allr + r0 * P; w.rew_act = (c->cfg.normalize_returns ? c->d_rew_raw : c->d_rew) + r0; w.done_f = c->d_done + r0; w.done_u8 = nullptr;
         w.ep_ret = c->d_ep_ret; w.ep_len = c->d_ep_len; w.eps = c->d_eps; w.ep_count = c->d_ep_count;
         w.eps_cap = c->eps_cap; w.err = c->d_err;
+        if (opp) { w.opp_out = c->d_opp_out; w.n_opp = c->n_opp; }
         WHIP(c, wide_env_step(c->cfg.env_kind, c->stream, w));
         if (opp) WTRY(opp_step_seats(c, t));
     }

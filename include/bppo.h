@@ -138,6 +138,18 @@ typedef struct {
     int32_t step;                /* loop iteration at which it ended */
 } bppo_eval_game;
 
+/* one finished opponent-pool game (OpponentEpisodeCompletion, ppo.rs:505-521): the seats as
+ * they were while the game was played, captured before the reshuffle (ppo.rs:871-917) */
+typedef struct {
+    int32_t env_index;
+    int32_t step;                /* rollout step t at which it ended */
+    int32_t learner_position;
+    int32_t n_players;           /* the seated player count P */
+    int32_t placement[BPPO_MAX_PLAYERS];              /* per seat, 1 = first; seats >= P: 0 */
+    int32_t position_to_opponent[BPPO_MAX_PLAYERS];   /* device model index per seat; -1 on the
+                                                       * learner's seat and on seats >= P */
+} bppo_opp_completion;
+
 typedef struct bppo_ctx bppo_ctx;
 
 /* ---- lifecycle ---------------------------------------------------------- */
@@ -155,6 +167,7 @@ size_t bppo_episode_size(void);
 size_t bppo_rollout_info_size(void);
 size_t bppo_eval_config_size(void);
 size_t bppo_eval_game_size(void);
+size_t bppo_opp_completion_size(void);
 
 /* ---- ActorCritic -------------------------------------------------------- */
 /* flat parameters in Burn record order: per Linear W[in][out] then b[out];
@@ -300,6 +313,25 @@ bppo_status bppo_opponents_set(bppo_ctx *ctx, int32_t n_models, const float *par
                                const int32_t *learner_pos, const int32_t *pos_to_opp, const int32_t *current_opp);
 /* the seat state after the last rollout's reshuffles */
 bppo_status bppo_opponents_get_envs(bppo_ctx *ctx, int32_t *learner_pos, int32_t *pos_to_opp);
+/* opponent_completions of the last rollout (ppo.rs:505-521, 871-917): every finished game of
+ * the envs [0, num_opponent_envs) whose env reported a game_outcome, with the placements and
+ * the seats it was played under, in the reference's order (step, then env index).  The
+ * rollout keeps as many records as it keeps episodes (num_envs * num_steps + 4096);
+ * games past that are counted but not kept.  out receives the first min(cap, recorded)
+ * records, *n = how many were recorded, *dropped = how many did not fit (either may be NULL;
+ * out may be NULL when cap is 0).  The records belong to the rollout bppo_rollout_episodes
+ * describes: a rollout bppo_train_steps ran ahead replaces both, bppo_opponents_set empties
+ * both, and a state setter that discards a pending rollout empties the records.
+ * BPPO_ERR_ARG when no opponents are set. */
+bppo_status bppo_opponents_completions(bppo_ctx *ctx, bppo_opp_completion *out, int32_t cap, int32_t *n,
+                                       int32_t *dropped);
+/* OpponentPool::queue_game_result (opponent_pool.rs:578-616) summed over those games, dropped
+ * ones included, per device model slot [n_models]: games = one per (game, opponent seat),
+ * wins = those where the learner placed better than that seat, swiss_points = the learner's
+ * P - placement added once per opponent seat.  Integers, so exact in any order; any array
+ * may be NULL.  (main.rs:755-803 feeds them to apply_pending_win_rate_updates.)
+ * BPPO_ERR_ARG when no opponents are set. */
+bppo_status bppo_opponents_results(bppo_ctx *ctx, int32_t *wins, int32_t *games, int64_t *swiss_points);
 
 /* Stats-mode evaluation on the device (eval.rs:1621-1877 run_stats_mode_env, the engine of
  * `eval --num-games` and of the tournament pods): plays cfg->num_games games between
