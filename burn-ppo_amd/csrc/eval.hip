@@ -4,29 +4,35 @@
 // (opponents.hip) with a temperature sampler, envs that can be frozen, game
 // outcomes captured before the auto-reset, and the games cap + freeze rule.
 //
+// One loop (evaluate_run) plays n_pods independent matchups (pods) of E envs each: pod k owns
+// envs [k E, (k + 1) E), its own RNG key and position, games counter and freeze state; only
+// the forward pass is shared, one model's rows from every pod being contiguous (DESIGN.md
+// section 7d).  bppo_evaluate_pods is that loop; bppo_evaluate is its one-pod case.
+//
 // Per loop iteration, on the context's stream:
 //   observe          rows, masks, player to move (k_wide_observe)
-//   k_eval_group     each active env's mover model seat_model[perm[player]]
-//                    (eval.rs:1697-1704), its row in the step's model-major order, its
-//                    temperature (eval.rs:1766) and, if it draws, its draw index: models
-//                    in ascending index, within a model the non-frozen envs in ascending
-//                    index (eval.rs:1685-1769)
-//   one host read    {games completed, active envs, group bases}: sizes the per-model
+//   k_eval_group     one block per pod: each active env's mover model seat_model[perm[player]]
+//                    (eval.rs:1697-1704), its temperature (eval.rs:1766), its rank among the
+//                    pod's rows of that model and, if it draws, its draw index: the pod's
+//                    slots ascending, within a slot the non-frozen envs in ascending index
+//                    (eval.rs:1685-1769); the (model, pod) row counts
+//   k_eval_scan      the counts scanned model-major, pod-minor: each env's row, the header
+//   one host read    {unfinished pods, error flags, group bases}: sizes the per-model
 //                    GEMMs and ends the loop (eval.rs:1670-1674)
 //   per model        rows sorted (k_opp_sort_rows), its obs normalizer
 //                    (eval.rs:1727-1734), wide_forward_actor, logits selected back
 //                    (k_opp_select); a random model's rows see zero logits (eval.rs:1749-1752)
-//   k_eval_sample    sample_with_temperature per row at word base + draw index
-//   env step         k_wide_step with the frozen mask and the outcome sink
-//   k_eval_finish    games recorded in env order up to the cap, seat -> checkpoint remap,
-//                    permutation rotation, move counts, freeze rule, RNG position
-//                    (eval.rs:1774-1869)
-// The RNG position lives on the device (as in the opponent-pool rollout).
+//   k_eval_sample    sample_with_temperature per row at the pod's word position + draw index
+//   env step         k_wide_step with the frozen mask, the outcome sink and per-env seeds
+//   k_eval_finish    one block per pod: games recorded in env order up to the cap, seat ->
+//                    checkpoint remap, permutation rotation, move counts, freeze rule, RNG
+//                    position (eval.rs:1774-1869)
+// The RNG positions live on the device (as in the opponent-pool rollout).
 //
-// bppo_evaluate_pods plays many such matchups (pods) in one loop: k_pods_group /
-// k_pods_scan / k_pods_finish replace the two one-block kernels with one block per pod,
-// every pod has its own RNG key, position and counters, and one model's rows from all pods
-// share a GEMM group.
+// A pod's slots are the host-built table slot_model, the one thing the two entry points
+// differ in: bppo_evaluate lists the seated models in ascending model index (the reference's
+// draw order), bppo_evaluate_pods by first appearance among the pod's seats (run_pod's
+// de-duplication).
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -37,27 +43,36 @@
 
 namespace bppo {
 
-constexpr int EV_MAX_MODELS = 15;
-constexpr int EV_THREADS = 1024;
+constexpr int EV_MAX_MODELS = 64;
+constexpr int EV_SINGLE_MAX_MODELS = 15;  // bppo_evaluate's documented limit (bppo.h)
+constexpr int EV_MAX_PODS = 1024;
+constexpr int EV_POD_THREADS = 1024;      // at most; a pod's block is its envs rounded up to whole waves
+constexpr int EV_SCAN_THREADS = 1024;
 constexpr int EV_ERR_ZERO_SUM = 16;   // d_err bit: the sampler's sum == 0.0 exit (bppo_eval.h temp_draws)
 
-// the step's small record, read by the host once per iteration
+// the step's small record, read by the host once per iteration; its size is independent of n_pods
 struct EvalHdr {
-    int32_t games, active, ndraw, pad;
-    int32_t gbase[EV_MAX_MODELS + 2];   // group g (0 frozen, 1 + model) owns rows [gbase[g], gbase[g + 1])
+    int32_t unfinished;                  // pods with games < num_games and an active env
+    int32_t err;                         // the context's error flags so far
+    int32_t gbase[EV_MAX_MODELS + 2];    // group g (0 frozen, 1 + model) owns rows [gbase[g], gbase[g + 1])
 };
 
 struct EvalState {
-    int N, P, K, nperm, num_games;
+    int n_pods, E, P, K, nperm, num_games, cap;
     bppo_eval::TempSched temp;
-    int32_t seat_model[BPPO_MAX_PLAYERS];
-    const int32_t *perm_tab;     // [nperm][P]: perm[player] = checkpoint
-    int32_t *perm_idx, *moves;   // [N]
-    uint8_t *frozen;             // [N]
-    int32_t *group, *gpos, *didx;   // [N]; didx: draw index or -1
-    float *tempv;                // [N]
+    const int32_t *perm_tab;             // [nperm][P]: perm[player] = checkpoint
+    const int32_t *seat_model;           // [n_pods][P] checkpoint -> model
+    const int32_t *slot_model;           // [n_pods][P] slot -> model, -1 past the pod's last slot
+    int32_t *perm_idx, *moves;           // [N]
+    uint8_t *frozen;                     // [N]
+    int32_t *group, *gpos, *didx;        // [N] 0 frozen / 1 + model; row; draw index from the pod's RNG position or -1
+    int32_t *lrank;                      // [N] rank among the pod's rows of its group
+    float *tempv;                        // [N]
+    int32_t *counts, *offs;              // [K + 1][n_pods] rows of (group, pod); their exclusive scan
+    int32_t *games, *active, *ndraw;     // [n_pods]
+    uint64_t *rngpos;                    // [n_pods]
     EvalHdr *hdr;
-    uint64_t *rngpos;
+    const int32_t *err;
 };
 
 // exclusive scan of a (rows, draws) pair packed in 64 bits over the block's threads in
@@ -82,73 +97,25 @@ __device__ __forceinline__ uint64_t block_scan_excl(uint64_t v, uint64_t *wsum, 
     return base + inc - v;
 }
 
-// One block; thread t owns envs [t per, (t + 1) per) so any N is covered, in env order.
-__global__ void __launch_bounds__(EV_THREADS) k_eval_group(EvalState s, const int32_t *players) {
-    __shared__ uint64_t wsum[EV_THREADS / 64];
-    const int tid = threadIdx.x;
-    const int per = (s.N + EV_THREADS - 1) / EV_THREADS;
-    const int e0 = min(s.N, tid * per), e1 = min(s.N, e0 + per);
-    for (int e = e0; e < e1; e++) {
-        int g = 0;
-        float temp = 0.0f;
-        int draws = 0;
-        if (!s.frozen[e]) {
-            const int cp = s.perm_tab[(size_t)s.perm_idx[e] * s.P + players[e]];   // eval.rs:1700-1701
-            g = 1 + s.seat_model[cp];                                               // :1704
-            temp = bppo_eval::get_temp(s.temp, s.moves[e]);                         // :1766
-            draws = bppo_eval::temp_draws(temp) ? 1 : 0;
-        }
-        s.group[e] = g;
-        s.tempv[e] = temp;
-        s.didx[e] = draws - 1;       // 0: draws (index below), -1: no draw
-    }
-    uint64_t rbase = 0, dbase = 0;   // rows / draws of the groups before g (the same in every thread)
-    for (int g = 0; g <= s.K; g++) {
-        uint32_t nr = 0, nd = 0;
-        for (int e = e0; e < e1; e++)
-            if (s.group[e] == g) { nr++; nd += s.didx[e] >= 0; }
-        uint64_t tot;
-        const uint64_t ex = block_scan_excl((uint64_t)nr | ((uint64_t)nd << 32), wsum, &tot);
-        uint32_t r = (uint32_t)rbase + (uint32_t)ex, d = (uint32_t)dbase + (uint32_t)(ex >> 32);
-        for (int e = e0; e < e1; e++)
-            if (s.group[e] == g) {
-                s.gpos[e] = (int32_t)r++;
-                if (s.didx[e] >= 0) s.didx[e] = (int32_t)d++;
-            }
-        if (tid == 0) s.hdr->gbase[g] = (int32_t)rbase;
-        rbase += (uint32_t)tot;
-        dbase += tot >> 32;
-    }
-    if (tid == 0) {
-        s.hdr->gbase[s.K + 1] = (int32_t)rbase;
-        s.hdr->ndraw = (int32_t)dbase;
-    }
-}
-
 struct EvalSampleArgs {
     int N;
     const float *logits;         // [N][A], env order
     const uint8_t *mask;         // [N][A]
-    const int32_t *group;        // 0: frozen (writes nothing); 1 + model
+    const int32_t *group;        // 0: frozen (writes nothing); 1 + model (null: every row model 0)
     const int32_t *didx;         // draw index or -1
     const float *temp;           // [N]
-    uint32_t random_models;      // bit k: model k is the random player (zero logits)
-    Key8 key;
-    uint64_t stream, base;
-    const uint64_t *dbase;       // the step's first word position from device memory (else base)
+    uint64_t random_models;      // bit k: model k is the random player (zero logits)
+    int pod_envs;                // env e belongs to pod e / pod_envs
+    const Key8 *pod_key;         // [pods]
+    const uint64_t *pod_rngpos;  // [pods] the step's first word position
+    uint64_t stream;             // ChaCha stream id: 0 in the evaluation loop
     int32_t *act;
     int32_t *used;               // [N] whether the row drew (may be null)
     int32_t *err;
-    // the POD variant only (bppo_evaluate_pods): env e belongs to pod e / pod_envs, whose key
-    // and word base replace key / dbase; bit k of random_models64: model k is the random player
-    int pod_envs = 0;
-    const Key8 *pod_key = nullptr;
-    const uint64_t *pod_rngpos = nullptr;
-    uint64_t random_models64 = 0;
 };
 
 // one row per lane; the row's word computed once; the sequential chains in registers
-template <int A, bool POD = false>
+template <int A>
 __global__ void __launch_bounds__(64) k_eval_sample(EvalSampleArgs g) {
     __shared__ MathLds T;
     T.load();
@@ -156,9 +123,7 @@ __global__ void __launch_bounds__(64) k_eval_sample(EvalSampleArgs g) {
     if (e >= g.N) return;
     const int grp = g.group ? g.group[e] : 1;
     if (grp == 0) return;                                   // frozen: never sampled again
-    bool rnd;
-    if constexpr (POD) rnd = (g.random_models64 >> (grp - 1)) & 1ull;
-    else rnd = (g.random_models >> (grp - 1)) & 1u;
+    const bool rnd = (g.random_models >> (grp - 1)) & 1ull;
     float x[A];
     uint8_t mk[A];
 #pragma unroll
@@ -171,13 +136,9 @@ __global__ void __launch_bounds__(64) k_eval_sample(EvalSampleArgs g) {
         x[a] = ok ? (rnd ? 0.0f : x[a]) : -INFINITY;        // eval.rs:230-238, :1749-1752
     }
     const int di = g.didx[e];
+    const int pod = e / g.pod_envs;
     uint32_t word = 0;
-    if constexpr (POD) {
-        const int pod = e / g.pod_envs;
-        if (di >= 0) word = chacha12_word(g.pod_key[pod], 0, g.pod_rngpos[pod] + (uint64_t)di);
-    } else {
-        if (di >= 0) word = chacha12_word(g.key, g.stream, (g.dbase ? *g.dbase : g.base) + (uint64_t)di);
-    }
+    if (di >= 0) word = chacha12_word(g.pod_key[pod], g.stream, g.pod_rngpos[pod] + (uint64_t)di);
     int used = 0;
     const int a = bppo_eval::sample_with_temperature<A>(x, first < 0 ? 0 : first, g.temp[e], word, &used, T);
     if (used != (di >= 0)) atomicOr(g.err, EV_ERR_ZERO_SUM);
@@ -187,13 +148,6 @@ __global__ void __launch_bounds__(64) k_eval_sample(EvalSampleArgs g) {
 
 static hipError_t eval_sample(int A, hipStream_t st, const EvalSampleArgs &g) {
     const dim3 grid((g.N + 63) / 64), block(64);
-    if (g.pod_key) {
-        if (A == C4_ACT) hipLaunchKernelGGL((k_eval_sample<C4_ACT, true>), grid, block, 0, st, g);
-        else if (A == LD_ACT) hipLaunchKernelGGL((k_eval_sample<LD_ACT, true>), grid, block, 0, st, g);
-        else if (A == SK_ACT) hipLaunchKernelGGL((k_eval_sample<SK_ACT, true>), grid, block, 0, st, g);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
     if (A == C4_ACT) hipLaunchKernelGGL(k_eval_sample<C4_ACT>, grid, block, 0, st, g);
     else if (A == LD_ACT) hipLaunchKernelGGL(k_eval_sample<LD_ACT>, grid, block, 0, st, g);
     else if (A == SK_ACT) hipLaunchKernelGGL(k_eval_sample<SK_ACT>, grid, block, 0, st, g);
@@ -241,155 +195,49 @@ __device__ __forceinline__ bppo_eval_game game_record(const int32_t *perm, int P
     return rec;
 }
 
-// After the env step (eval.rs:1774-1869).  One block, thread t owns envs [t per, (t + 1) per).
-__global__ void __launch_bounds__(EV_THREADS) k_eval_finish(EvalState s, int step, const uint8_t *done,
-                                                            const EvalOutcome *sink, bppo_eval_game *games,
-                                                            int games_cap) {
-    __shared__ uint64_t wsum[EV_THREADS / 64];
-    const int tid = threadIdx.x;
-    const int per = (s.N + EV_THREADS - 1) / EV_THREADS;
-    const int e0 = min(s.N, tid * per), e1 = min(s.N, e0 + per);
-    const int g0 = s.hdr->games;
-    uint32_t nd = 0, na = 0;
-    for (int e = e0; e < e1; e++) { nd += done[e] != 0; na += s.frozen[e] == 0; }
-    uint64_t tot;
-    const uint64_t ex = block_scan_excl((uint64_t)nd | ((uint64_t)na << 32), wsum, &tot);   // (hdr read above: barrier inside)
-    const int ND = (int)(uint32_t)tot, ACT = (int)(tot >> 32);
-    // finished games are recorded in env order while games_completed < num_games (:1783-1789)
-    const int nrec = min(ND, max(0, s.num_games - g0));
-    const int g1 = g0 + nrec;
-    // freeze rule (:1841-1869): active > remaining freezes the excess, this step's finished
-    // envs first (env order), then any non-frozen env in index order
-    const int remaining = max(0, s.num_games - g1);
-    const int to_freeze = ACT > remaining ? ACT - remaining : 0;
-    const int f1 = min(to_freeze, ND), f2 = to_freeze - f1;
-    int k = (int)(uint32_t)ex;
-    uint32_t alive = 0;
-    for (int e = e0; e < e1; e++) {
-        int mv = s.moves[e] + 1;                                    // every env, frozen included (:1775-1777)
-        if (done[e]) {
-            if (k < nrec) {
-                const int pi = s.perm_idx[e];
-                const bppo_eval_game rec = game_record(s.perm_tab + (size_t)pi * s.P, s.P, sink[e], e, pi, step);
-                if (g0 + k < games_cap) games[g0 + k] = rec;
-                mv = 0;                                              // :1830
-                s.perm_idx[e] = (pi + 1) % s.nperm;                  // :1831
-            }                                                        // past the cap: dropped, nothing touched (:1785-1787)
-            if (k < f1) s.frozen[e] = 1;
-            k++;
-        }
-        s.moves[e] = mv;
-        alive += s.frozen[e] == 0;
-    }
-    if (f2 > 0) {                                                   // the same in every thread
-        uint64_t t2;
-        int r = (int)(uint32_t)block_scan_excl((uint64_t)alive, wsum, &t2);
-        for (int e = e0; e < e1; e++)
-            if (!s.frozen[e]) {
-                if (r < f2) s.frozen[e] = 1;
-                r++;
-            }
-    }
-    if (tid == 0) {
-        s.hdr->games = g1;
-        s.hdr->active = ACT - to_freeze;
-        *s.rngpos += (uint64_t)s.hdr->ndraw;                       // the step's draws
-    }
-}
-
-__global__ void k_eval_init(EvalState s, uint64_t pos) {
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < s.N; e += gridDim.x * blockDim.x) {
-        s.perm_idx[e] = e % s.nperm;          // eval.rs:1662
-        s.moves[e] = 0;
-        s.frozen[e] = 0;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        s.hdr->games = 0;
-        s.hdr->active = s.N;
-        s.hdr->ndraw = 0;
-        *s.rngpos = pos;
-    }
-}
-
-// ---------------------------------------------------------------- pods -----
-// bppo_evaluate_pods: n_pods independent matchups of E envs each in one loop.  Pod k owns
-// envs [k E, (k + 1) E) and its own RNG (key, position), games counter and freeze state;
-// only the forward pass is shared: one model's rows from every pod are contiguous.
-constexpr int EVP_MAX_MODELS = 64;
-constexpr int EVP_MAX_PODS = 1024;
-constexpr int EVP_POD_THREADS = 256;      // at most; a pod's block is its envs rounded up to whole waves
-constexpr int EVP_SCAN_THREADS = 1024;
-
-// the step's small record, read by the host once per iteration; its size is independent of n_pods
-struct PodHdr {
-    int32_t unfinished;                  // pods with games < num_games and an active env
-    int32_t err;                         // the context's error flags so far
-    int32_t gbase[EVP_MAX_MODELS + 2];   // group g (0 frozen, 1 + global model) owns rows [gbase[g], gbase[g + 1])
-};
-
-struct PodState {
-    int n_pods, E, P, K, nperm, num_games, cap;
-    bppo_eval::TempSched temp;
-    const int32_t *perm_tab;             // [nperm][P]
-    const int32_t *seat_model;           // [n_pods][P] checkpoint -> global model
-    const int32_t *seat_slot;            // [n_pods][P] checkpoint -> the pod's local slot
-    const int32_t *slot_model;           // [n_pods][P] local slot -> global model, -1 past the pod's last slot
-    int32_t *perm_idx, *moves;           // [N]
-    uint8_t *frozen;                     // [N]
-    int32_t *group, *gpos, *didx;        // [N] as in EvalState; didx relative to the pod's RNG position
-    int32_t *slot, *lrank;               // [N] 0 frozen / 1 + local slot; rank among the pod's rows of its group
-    float *tempv;                        // [N]
-    int32_t *counts, *offs;              // [K + 1][n_pods] rows of (group, pod); their exclusive scan
-    int32_t *games, *active, *ndraw;     // [n_pods]
-    uint64_t *rngpos;                    // [n_pods]
-    PodHdr *hdr;
-    const int32_t *err;
-};
-
-// One block per pod; thread t owns envs [t per, (t + 1) per) of the pod, so any E is covered
-// in env order.  The draw order is the single call's on the pod's local models: local
-// slots ascending, within a slot the pod's envs ascending.
-__global__ void __launch_bounds__(EVP_POD_THREADS) k_pods_group(PodState s, const int32_t *players) {
-    __shared__ uint64_t wsum[EVP_POD_THREADS / 64];
+// One block per pod.  The draw order: the pod's slots ascending (slot_model; a pod's slots
+// name distinct models, so an env's group tells its slot), within a slot its envs ascending:
+// thread t owns envs [t per, (t + 1) per) of the pod, so any E is covered in env order.
+__global__ void __launch_bounds__(EV_POD_THREADS) k_eval_group(EvalState s, const int32_t *players) {
+    __shared__ uint64_t wsum[EV_POD_THREADS / 64];
     const int pod = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     const int per = (s.E + nt - 1) / nt;
     const int j0 = min(s.E, tid * per), j1 = min(s.E, j0 + per);
     const size_t b = (size_t)pod * s.E;
-    const int32_t *sm = s.seat_model + (size_t)pod * s.P, *ss = s.seat_slot + (size_t)pod * s.P;
+    const int32_t *sm = s.seat_model + (size_t)pod * s.P;
     for (int g = tid; g <= s.K; g += nt) s.counts[(size_t)g * s.n_pods + pod] = 0;
-    for (int j = j0; j < j1; j++) {
+    for (int j = tid; j < s.E; j += nt) {    // each env by itself: consecutive threads, consecutive envs
         const size_t e = b + j;
-        int g = 0, sl = 0;
+        int g = 0;
         float temp = 0.0f;
         int draws = 0;
         if (!s.frozen[e]) {
             const int cp = s.perm_tab[(size_t)s.perm_idx[e] * s.P + players[e]];   // eval.rs:1700-1701
             g = 1 + sm[cp];                                                         // :1704
-            sl = 1 + ss[cp];
             temp = bppo_eval::get_temp(s.temp, s.moves[e]);                         // :1766
             draws = bppo_eval::temp_draws(temp) ? 1 : 0;
         }
         s.group[e] = g;
-        s.slot[e] = sl;
         s.tempv[e] = temp;
         s.didx[e] = draws - 1;       // 0: draws (index below), -1: no draw
     }
+    __syncthreads();                 // group, didx of the thread's own run
     uint32_t dbase = 0;              // draws of the slots before sl (the same in every thread)
     for (int sl = 0; sl <= s.P; sl++) {
-        const int model = sl == 0 ? -1 : s.slot_model[(size_t)pod * s.P + sl - 1];
-        if (sl > 0 && model < 0) break;                       // past the pod's last slot (block-uniform)
+        const int g = sl == 0 ? 0 : 1 + s.slot_model[(size_t)pod * s.P + sl - 1];
+        if (sl > 0 && g == 0) break;                          // past the pod's last slot (block-uniform)
         uint32_t nr = 0, nd = 0;
         for (int j = j0; j < j1; j++)
-            if (s.slot[b + j] == sl) { nr++; nd += s.didx[b + j] >= 0; }
+            if (s.group[b + j] == g) { nr++; nd += s.didx[b + j] >= 0; }
         uint64_t tot;
         const uint64_t ex = block_scan_excl((uint64_t)nr | ((uint64_t)nd << 32), wsum, &tot);
         uint32_t r = (uint32_t)ex, d = dbase + (uint32_t)(ex >> 32);
         for (int j = j0; j < j1; j++)
-            if (s.slot[b + j] == sl) {
+            if (s.group[b + j] == g) {
                 s.lrank[b + j] = (int32_t)r++;
                 if (s.didx[b + j] >= 0) s.didx[b + j] = (int32_t)d++;
             }
-        if (tid == 0) s.counts[(size_t)(model + 1) * s.n_pods + pod] = (int32_t)(uint32_t)tot;
+        if (tid == 0) s.counts[(size_t)g * s.n_pods + pod] = (int32_t)(uint32_t)tot;
         dbase += (uint32_t)(tot >> 32);
     }
     if (tid == 0) s.ndraw[pod] = (int32_t)dbase;
@@ -397,12 +245,12 @@ __global__ void __launch_bounds__(EVP_POD_THREADS) k_pods_group(PodState s, cons
 
 // One block: the (group, pod) row counts scanned group-major, pod-minor, so a model's rows
 // from all pods are contiguous with the pods ascending; each env's global row; the header.
-__global__ void __launch_bounds__(EVP_SCAN_THREADS) k_pods_scan(PodState s) {
-    __shared__ uint64_t wsum[EVP_SCAN_THREADS / 64];
+__global__ void __launch_bounds__(EV_SCAN_THREADS) k_eval_scan(EvalState s) {
+    __shared__ uint64_t wsum[EV_SCAN_THREADS / 64];
     __shared__ int unfinished;
     const int tid = threadIdx.x;
     const int n = (s.K + 1) * s.n_pods;
-    const int per = (n + EVP_SCAN_THREADS - 1) / EVP_SCAN_THREADS;
+    const int per = (n + EV_SCAN_THREADS - 1) / EV_SCAN_THREADS;
     const int i0 = min(n, tid * per), i1 = min(n, i0 + per);
     if (tid == 0) unfinished = 0;
     uint32_t sum = 0;
@@ -410,12 +258,12 @@ __global__ void __launch_bounds__(EVP_SCAN_THREADS) k_pods_scan(PodState s) {
     uint64_t tot;
     uint32_t r = (uint32_t)block_scan_excl((uint64_t)sum, wsum, &tot);
     for (int i = i0; i < i1; i++) { s.offs[i] = (int32_t)r; r += (uint32_t)s.counts[i]; }
-    for (int k = tid; k < s.n_pods; k += EVP_SCAN_THREADS)
+    for (int k = tid; k < s.n_pods; k += EV_SCAN_THREADS)
         if (s.games[k] < s.num_games && s.active[k] > 0) atomicAdd(&unfinished, 1);
     __syncthreads();                 // offs, unfinished
-    for (int g = tid; g <= s.K; g += EVP_SCAN_THREADS) s.hdr->gbase[g] = s.offs[(size_t)g * s.n_pods];
+    for (int g = tid; g <= s.K; g += EV_SCAN_THREADS) s.hdr->gbase[g] = s.offs[(size_t)g * s.n_pods];
     const int N = s.n_pods * s.E;
-    for (int e = tid; e < N; e += EVP_SCAN_THREADS)
+    for (int e = tid; e < N; e += EV_SCAN_THREADS)
         s.gpos[e] = s.offs[(size_t)s.group[e] * s.n_pods + e / s.E] + s.lrank[e];
     if (tid == 0) {
         s.hdr->gbase[s.K + 1] = (int32_t)(uint32_t)tot;
@@ -424,11 +272,12 @@ __global__ void __launch_bounds__(EVP_SCAN_THREADS) k_pods_scan(PodState s) {
     }
 }
 
-// k_eval_finish per pod (eval.rs:1774-1869) against the pod's own counters; games go to
-// games[pod cap + ...] with env_index the index within the pod
-__global__ void __launch_bounds__(EVP_POD_THREADS) k_pods_finish(PodState s, int step, const uint8_t *done,
+// After the env step (eval.rs:1774-1869).  One block per pod against the pod's own counters,
+// thread t owning envs [t per, (t + 1) per) of the pod; games go to games[pod cap + ...] with
+// env_index the index within the pod
+__global__ void __launch_bounds__(EV_POD_THREADS) k_eval_finish(EvalState s, int step, const uint8_t *done,
                                                                  const EvalOutcome *sink, bppo_eval_game *games) {
-    __shared__ uint64_t wsum[EVP_POD_THREADS / 64];
+    __shared__ uint64_t wsum[EV_POD_THREADS / 64];
     const int pod = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     if (s.active[pod] == 0) return;                  // a finished pod: every env frozen (block-uniform)
     const int per = (s.E + nt - 1) / nt;
@@ -480,7 +329,7 @@ __global__ void __launch_bounds__(EVP_POD_THREADS) k_pods_finish(PodState s, int
     }
 }
 
-__global__ void k_pods_init(PodState s, uint64_t pos) {
+__global__ void k_eval_init(EvalState s, uint64_t pos) {
     const int N = s.n_pods * s.E;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < N; e += gridDim.x * blockDim.x) {
         s.perm_idx[e] = (e % s.E) % s.nperm;  // eval.rs:1662, per pod
@@ -517,7 +366,6 @@ static std::vector<int32_t> generate_permutations(int n) {
 struct EvalBuffers {
     std::vector<void *> dev;
     EvalHdr *h_hdr = nullptr;
-    PodHdr *h_pod = nullptr;
     template <class T>
     hipError_t alloc(T **p, size_t n) {
         *p = nullptr;
@@ -528,7 +376,6 @@ struct EvalBuffers {
     ~EvalBuffers() {
         for (void *p : dev) (void)hipFree(p);
         if (h_hdr) (void)hipHostFree(h_hdr);
-        if (h_pod) (void)hipHostFree(h_pod);
     }
 };
 
@@ -593,20 +440,25 @@ extern "C" bppo_status bppo_debug_eval_sample(int32_t device, int32_t A, int32_t
     float *d_l = nullptr, *d_t = nullptr;
     uint8_t *d_m = nullptr;
     int32_t *d_di = nullptr, *d_a = nullptr, *d_u = nullptr, *d_e = nullptr;
+    Key8 *d_key = nullptr;
+    uint64_t *d_pos = nullptr;
     int32_t err = 0;
     if (buf.alloc(&d_l, nA) != hipSuccess || buf.alloc(&d_m, nA) != hipSuccess || buf.alloc(&d_t, (size_t)B) != hipSuccess ||
         buf.alloc(&d_di, (size_t)B) != hipSuccess || buf.alloc(&d_a, (size_t)B) != hipSuccess ||
-        buf.alloc(&d_u, (size_t)B) != hipSuccess || buf.alloc(&d_e, 1) != hipSuccess)
+        buf.alloc(&d_u, (size_t)B) != hipSuccess || buf.alloc(&d_e, 1) != hipSuccess ||
+        buf.alloc(&d_key, 1) != hipSuccess || buf.alloc(&d_pos, 1) != hipSuccess)
         return BPPO_ERR_HIP;
     if (hipMemcpy(d_l, logits, nA * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_m, masks, nA, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_t, temps, 4ull * B, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_di, didx.data(), 4ull * B, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_key, &key, sizeof(Key8), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_pos, &word_pos, 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(d_e, 0, 4) != hipSuccess)
         return BPPO_ERR_HIP;
-    EvalSampleArgs g;
+    EvalSampleArgs g;                       // one pod of B rows, all of model 0
     g.N = B; g.logits = d_l; g.mask = d_m; g.group = nullptr; g.didx = d_di; g.temp = d_t; g.random_models = 0;
-    g.key = key; g.stream = stream; g.base = word_pos; g.dbase = nullptr; g.act = d_a; g.used = d_u; g.err = d_e;
+    g.pod_envs = B; g.pod_key = d_key; g.pod_rngpos = d_pos; g.stream = stream; g.act = d_a; g.used = d_u; g.err = d_e;
     if (eval_sample(A, nullptr, g) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(actions, d_a, 4ull * B, hipMemcpyDeviceToHost) != hipSuccess ||
         (draws_used && hipMemcpy(draws_used, d_u, 4ull * B, hipMemcpyDeviceToHost) != hipSuccess) ||
@@ -615,37 +467,47 @@ extern "C" bppo_status bppo_debug_eval_sample(int32_t device, int32_t A, int32_t
     return (err & EV_ERR_ZERO_SUM) ? BPPO_ERR_NONFINITE : BPPO_OK;
 }
 
-extern "C" bppo_status bppo_evaluate(bppo_ctx *c, const bppo_eval_config *cfg, int32_t n_models, const float *params,
-                                     const double *norm_mean, const double *norm_m2, const double *norm_count,
-                                     const int32_t *is_random, const int32_t *seat_model, int32_t n_checkpoints,
-                                     bppo_eval_game *games, int32_t cap, int32_t *n_games, uint64_t *rng_word_pos) {
-    if (!c) return BPPO_ERR_ARG;
-    if (!c->wide || c->cfg.env_kind == BPPO_ENV_CARTPOLE) {
-        c->err = "evaluate: multi-player envs only (no stats mode for CartPole)";
-        return BPPO_ERR_UNSUPPORTED;
-    }
-    if (!cfg || !seat_model || !n_games || (cap > 0 && !games) || cap < 0) { c->err = "evaluate: NULL argument"; return BPPO_ERR_ARG; }
-    if (cfg->num_games < 0 || cfg->max_steps < 0) { c->err = "evaluate: num_games and max_steps must not be negative"; return BPPO_ERR_ARG; }
-    if (n_models < 1 || n_models > EV_MAX_MODELS) { c->err = "evaluate: 1..15 models"; return BPPO_ERR_ARG; }
-    const int P = c->Pa, N = c->N, A = c->A, D = c->D, L = c->L, K = n_models;
-    // the reference's permutations are over 0..num_players and a further checkpoint panics
-    // (eval.rs:1801-1804), fewer fail its assert (:1640-1643)
-    if (n_checkpoints != P) { c->err = "evaluate: n_checkpoints must equal the seated player count"; return BPPO_ERR_ARG; }
-    uint32_t random_models = 0;
+static uint64_t random_mask(const int32_t *is_random, int K) {
+    uint64_t m = 0;
     for (int k = 0; k < K; k++)
-        if (is_random && is_random[k]) random_models |= 1u << k;
+        if (is_random && is_random[k]) m |= 1ull << k;
+    return m;
+}
+
+// One pod's slots from its P seats: slot_model (-1 on entry) = the distinct seated models in
+// first-appearance order, or in ascending model index.
+static void pod_slots(const int32_t *seat_model, int P, bool ascending, int32_t *slot_model) {
+    int n = 0;
     for (int p = 0; p < P; p++)
-        if (seat_model[p] < 0 || seat_model[p] >= K) { c->err = "evaluate: seat_model names a model out of range"; return BPPO_ERR_ARG; }
-    if (random_models != (1u << K) - 1u && !params) { c->err = "evaluate: model parameters required"; return BPPO_ERR_ARG; }
+        if (std::find(slot_model, slot_model + n, seat_model[p]) == slot_model + n) slot_model[n++] = seat_model[p];
+    if (ascending) std::sort(slot_model, slot_model + n);
+}
+
+// The evaluation loop behind both entry points, which have checked their arguments: n_pods
+// matchups of E envs on the context's n_pods * E envs.  slot_model [n_pods][P]: each pod's
+// draw order (EvalState); who: the prefix of the error messages.
+static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_eval_config *cfg, int K,
+                                const float *params, const double *norm_mean, const double *norm_m2,
+                                const double *norm_count, uint64_t random_models, int n_pods, int E,
+                                const uint64_t *pod_seeds, const int32_t *pod_seat_model,
+                                const std::vector<int32_t> &slot_model, bppo_eval_game *games, int cap_per_pod,
+                                int32_t *n_games, uint64_t *rng_word_pos) {
+    const int P = c->Pa, N = c->N, A = c->A, D = c->D, L = c->L;
     drop_prefetch(c);
     if (!c->gae_done) c->collected = 0;       // a rollout not yet bootstrapped would read the evaluation's envs
-    *n_games = 0;
+    for (int k = 0; k < n_pods; k++) n_games[k] = 0;
 
-    // RNG (eval.rs:1646-1648): base_seed = rng.next_u64(), words 0 and 1, low word first
-    const Key8 key = seed_key(cfg->seed);
-    uint32_t blk0[16];
-    chacha12_block(key, 0, 0, blk0);
-    const uint64_t base_seed = ((uint64_t)blk0[1] << 32) | (uint64_t)blk0[0];
+    // per pod: StdRng(pod_seeds[k]); base_seed = rng.next_u64(), words 0 and 1, low word first,
+    // seeds its envs (eval.rs:1646-1648)
+    std::vector<Key8> keys((size_t)n_pods);
+    std::vector<uint64_t> env_seed((size_t)N);
+    for (int k = 0; k < n_pods; k++) {
+        keys[k] = seed_key(pod_seeds[k]);
+        uint32_t blk0[16];
+        chacha12_block(keys[k], 0, 0, blk0);
+        const uint64_t base_seed = ((uint64_t)blk0[1] << 32) | (uint64_t)blk0[0];
+        for (int j = 0; j < E; j++) env_seed[(size_t)k * E + j] = base_seed + (uint64_t)j;
+    }
 
     const std::vector<int32_t> perms = generate_permutations(P);
     const int nperm = (int)(perms.size() / (size_t)P);
@@ -653,188 +515,7 @@ extern "C" bppo_status bppo_evaluate(bppo_ctx *c, const bppo_eval_config *cfg, i
 
     EvalBuffers buf;
     EvalState s{};
-    int32_t *d_perm_tab = nullptr;
-    float *d_params = nullptr, *d_oxc = nullptr, *d_ologits = nullptr;
-    double *d_on = nullptr;
-    EvalOutcome *d_sink = nullptr;
-    bppo_eval_game *d_games = nullptr;
-    const int games_cap = std::min(cap, cfg->num_games);
-    BPPO_HIP(c, buf.alloc(&d_perm_tab, perms.size()));
-    BPPO_HIP(c, buf.alloc(&s.perm_idx, (size_t)N));
-    BPPO_HIP(c, buf.alloc(&s.moves, (size_t)N));
-    BPPO_HIP(c, buf.alloc(&s.frozen, (size_t)N));
-    BPPO_HIP(c, buf.alloc(&s.group, (size_t)N));
-    BPPO_HIP(c, buf.alloc(&s.gpos, (size_t)N));
-    BPPO_HIP(c, buf.alloc(&s.didx, (size_t)N));
-    BPPO_HIP(c, buf.alloc(&s.tempv, (size_t)N));
-    BPPO_HIP(c, buf.alloc(&s.hdr, 1));
-    BPPO_HIP(c, buf.alloc(&s.rngpos, 1));
-    BPPO_HIP(c, buf.alloc(&d_params, np * K));
-    BPPO_HIP(c, buf.alloc(&d_on, (size_t)(2 * D + 1) * K));
-    BPPO_HIP(c, buf.alloc(&d_oxc, (size_t)N * L));
-    BPPO_HIP(c, buf.alloc(&d_ologits, (size_t)N * A));
-    BPPO_HIP(c, buf.alloc(&d_sink, (size_t)N));
-    BPPO_HIP(c, buf.alloc(&d_games, (size_t)games_cap));
-    BPPO_HIP(c, hipHostMalloc((void **)&buf.h_hdr, sizeof(EvalHdr)));
-    s.N = N; s.P = P; s.K = K; s.nperm = nperm; s.num_games = cfg->num_games;
-    s.temp = bppo_eval::TempSched{cfg->temp_initial, cfg->temp_final, cfg->temp_cutoff, cfg->temp_decay};
-    for (int p = 0; p < BPPO_MAX_PLAYERS; p++) s.seat_model[p] = p < P ? seat_model[p] : 0;
-    s.perm_tab = d_perm_tab;
-
-    // models: uploads ordered on the context's stream, drained before the host arrays may go
-    std::vector<int> has_norm((size_t)K, 0);
-    std::vector<double> on((size_t)(2 * D + 1) * K, 0.0);
-    for (int k = 0; k < K; k++) {
-        if ((random_models >> k) & 1u) continue;
-        BPPO_HIP(c, hipMemcpyAsync(d_params + (size_t)k * np, params + (size_t)k * np, sizeof(float) * np,
-                                   hipMemcpyHostToDevice, c->stream));
-        if (!norm_count || norm_count[k] < 2.0 || !norm_mean || !norm_m2) continue;
-        has_norm[k] = 1;
-        std::memcpy(&on[(size_t)k * (2 * D + 1)], norm_mean + (size_t)k * D, sizeof(double) * D);
-        std::memcpy(&on[(size_t)k * (2 * D + 1) + D], norm_m2 + (size_t)k * D, sizeof(double) * D);
-        on[(size_t)k * (2 * D + 1) + 2 * D] = norm_count[k];
-    }
-    BPPO_HIP(c, hipMemcpyAsync(d_on, on.data(), sizeof(double) * on.size(), hipMemcpyHostToDevice, c->stream));
-    BPPO_HIP(c, hipMemcpyAsync(d_perm_tab, perms.data(), sizeof(int32_t) * perms.size(), hipMemcpyHostToDevice, c->stream));
-    BPPO_HIP(c, hipMemsetAsync(c->d_err, 0, 4, c->stream));
-    BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
-    hipLaunchKernelGGL(k_eval_init, dim3(std::min((N + 255) / 256, 1024)), dim3(256), 0, c->stream, s, (uint64_t)2);
-    TRY(launch_check(c, "k_eval_init"));
-    // VecEnv::new (E::new(base_seed + i) and a reset), then set_all_num_players resets every
-    // env again (env.rs:281-302, 313-326); E::new's reward shaping is the zero schedule
-    // (liars_dice.rs:461-463, skull.rs:1062-1065); Skull is seated with the context's player_count
-    BPPO_HIP(c, wide_env_reset(c->cfg.env_kind, c->stream, N, base_seed, P, c->d_wstate, c->d_env_pos, c->d_ep_ret,
-                               c->d_ep_len));
-    BPPO_HIP(c, wide_env_reset_again(c->cfg.env_kind, c->stream, N, base_seed, c->d_wstate, c->d_env_pos));
-
-    auto observe_group = [&]() -> bppo_status {
-        BPPO_HIP(c, wide_env_observe(c->cfg.env_kind, c->G > 0, c->stream, N, c->d_wstate, c->d_bxc, c->d_bmask,
-                                     c->d_bplayers));
-        hipLaunchKernelGGL(k_eval_group, dim3(1), dim3(EV_THREADS), 0, c->stream, s, c->d_bplayers);
-        TRY(launch_check(c, "k_eval_group"));
-        BPPO_HIP(c, hipMemcpyAsync(buf.h_hdr, s.hdr, sizeof(EvalHdr), hipMemcpyDeviceToHost, c->stream));
-        BPPO_HIP(c, hipStreamSynchronize(c->stream));
-        return BPPO_OK;
-    };
-    TRY(observe_group());
-    bppo_status st = BPPO_OK;
-    for (int step = 0;; step++) {
-        const EvalHdr &h = *buf.h_hdr;
-        if (h.games >= cfg->num_games || h.active == 0) break;        // eval.rs:1670-1674
-        if (step >= cfg->max_steps) { c->err = "evaluate: max_steps exceeded before num_games games were played"; st = BPPO_ERR_ARG; break; }
-        const int32_t *gb = h.gbase;
-        bool any_fwd = false;
-        for (int k = 0; k < K; k++) any_fwd = any_fwd || (!((random_models >> k) & 1u) && gb[k + 2] > gb[k + 1]);
-        if (any_fwd) {
-            TRY(opp_sort_rows(c, s.group, s.gpos, c->d_bxc, d_oxc));
-            for (int k = 0; k < K; k++) {
-                const int r0 = gb[k + 1], rows = gb[k + 2] - gb[k + 1];
-                if (rows <= 0 || ((random_models >> k) & 1u)) continue;
-                float *x = d_oxc + (size_t)r0 * L;
-                if (has_norm[k]) TRY(launch_obs_norm_rows_on(c, rows, x + c->G, L, nullptr, d_on + (size_t)k * (2 * D + 1)));
-                TRY(wide_forward_actor(c, rows, x, L, d_params + (size_t)k * np, d_ologits + (size_t)r0 * A));
-            }
-            TRY(opp_select(c, s.group, s.gpos, d_ologits, c->d_logits));
-        }
-        EvalSampleArgs g;
-        g.N = N; g.logits = c->d_logits; g.mask = c->d_bmask; g.group = s.group; g.didx = s.didx; g.temp = s.tempv;
-        g.random_models = random_models; g.key = key; g.stream = 0; g.base = 0; g.dbase = s.rngpos;
-        g.act = c->d_act_in; g.used = nullptr; g.err = c->d_err;
-        BPPO_HIP(c, eval_sample(A, c->stream, g));
-        WideStepArgs w;
-        w.N = N; w.t = step; w.state = c->d_wstate; w.env_pos = c->d_env_pos; w.seed_base = base_seed;
-        w.actions = c->d_act_in; w.shaping = 0.0f;
-        w.all_r = nullptr; w.rew_act = nullptr; w.done_f = nullptr; w.done_u8 = c->d_scr_d;
-        w.ep_ret = c->d_ep_ret; w.ep_len = c->d_ep_len; w.eps = c->d_eps; w.ep_count = c->d_ep_count;
-        w.eps_cap = 0; w.err = c->d_err;
-        w.frozen = s.frozen; w.sink = d_sink;
-        BPPO_HIP(c, wide_env_step(c->cfg.env_kind, c->stream, w));
-        hipLaunchKernelGGL(k_eval_finish, dim3(1), dim3(EV_THREADS), 0, c->stream, s, step, c->d_scr_d, d_sink, d_games,
-                           games_cap);
-        TRY(launch_check(c, "k_eval_finish"));
-        TRY(observe_group());
-    }
-    // results: the games, the RNG position, the error flags; the episode counter back to zero
-    const int ng = std::min<int>(buf.h_hdr->games, games_cap);
-    uint64_t pos = 0;
-    int32_t err = 0;
-    if (ng > 0) BPPO_HIP(c, hipMemcpyAsync(games, d_games, sizeof(bppo_eval_game) * (size_t)ng, hipMemcpyDeviceToHost, c->stream));
-    BPPO_HIP(c, hipMemcpyAsync(&pos, s.rngpos, 8, hipMemcpyDeviceToHost, c->stream));
-    BPPO_HIP(c, hipMemcpyAsync(&err, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
-    BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
-    BPPO_HIP(c, hipStreamSynchronize(c->stream));
-    *n_games = buf.h_hdr->games;
-    if (rng_word_pos) *rng_word_pos = pos;
-    if (st != BPPO_OK) return st;
-    if (err & 8) { c->err = "evaluate: an action outside the env's action mask"; return BPPO_ERR_ARG; }
-    if (err & EV_ERR_ZERO_SUM) { c->err = "evaluate: the sampler's softmax sum was zero"; return BPPO_ERR_NONFINITE; }
-    return BPPO_OK;
-}
-
-extern "C" bppo_status bppo_evaluate_pods(bppo_ctx *c, const bppo_eval_config *cfg, int32_t n_models, const float *params,
-                                          const double *norm_mean, const double *norm_m2, const double *norm_count,
-                                          const int32_t *is_random, int32_t n_pods, int32_t envs_per_pod,
-                                          const uint64_t *pod_seeds, const int32_t *pod_seat_model,
-                                          bppo_eval_game *games, int32_t cap_per_pod, int32_t *n_games,
-                                          uint64_t *rng_word_pos) {
-    if (!c) return BPPO_ERR_ARG;
-    if (!c->wide || c->cfg.env_kind == BPPO_ENV_CARTPOLE) {
-        c->err = "evaluate_pods: multi-player envs only (no stats mode for CartPole)";
-        return BPPO_ERR_UNSUPPORTED;
-    }
-    if (!cfg || !pod_seeds || !pod_seat_model || !n_games || (cap_per_pod > 0 && !games) || cap_per_pod < 0) {
-        c->err = "evaluate_pods: NULL argument";
-        return BPPO_ERR_ARG;
-    }
-    if (cfg->num_games < 0 || cfg->max_steps < 0) { c->err = "evaluate_pods: num_games and max_steps must not be negative"; return BPPO_ERR_ARG; }
-    if (n_models < 1 || n_models > EVP_MAX_MODELS) { c->err = "evaluate_pods: 1..64 models"; return BPPO_ERR_ARG; }
-    if (n_pods < 1 || n_pods > EVP_MAX_PODS) { c->err = "evaluate_pods: 1..1024 pods"; return BPPO_ERR_ARG; }
-    const int P = c->Pa, N = c->N, A = c->A, D = c->D, L = c->L, K = n_models, E = envs_per_pod;
-    if (E < 1 || (int64_t)n_pods * E != (int64_t)N) {
-        c->err = "evaluate_pods: n_pods * envs_per_pod must equal the context's num_envs";
-        return BPPO_ERR_ARG;
-    }
-    uint64_t random_models = 0;
-    for (int k = 0; k < K; k++)
-        if (is_random && is_random[k]) random_models |= 1ull << k;
-    for (int i = 0; i < n_pods * P; i++)
-        if (pod_seat_model[i] < 0 || pod_seat_model[i] >= K) { c->err = "evaluate_pods: pod_seat_model names a model out of range"; return BPPO_ERR_ARG; }
-    const uint64_t all_models = K == 64 ? ~0ull : (1ull << K) - 1ull;
-    if (random_models != all_models && !params) { c->err = "evaluate_pods: model parameters required"; return BPPO_ERR_ARG; }
-    drop_prefetch(c);
-    if (!c->gae_done) c->collected = 0;       // a rollout not yet bootstrapped would read the evaluation's envs
-    for (int k = 0; k < n_pods; k++) n_games[k] = 0;
-
-    // per pod: StdRng(pod_seeds[k]); words 0 and 1 seed its envs (eval.rs:1646-1648); the local
-    // slot of a model is the rank of its first appearance among the pod's seats (run_pod's
-    // de-duplication, tournament.rs:1811-1838)
-    std::vector<Key8> keys((size_t)n_pods);
-    std::vector<uint64_t> env_seed((size_t)N);
-    std::vector<int32_t> seat_slot((size_t)n_pods * P), slot_model((size_t)n_pods * P, -1);
-    for (int k = 0; k < n_pods; k++) {
-        keys[k] = seed_key(pod_seeds[k]);
-        uint32_t blk0[16];
-        chacha12_block(keys[k], 0, 0, blk0);
-        const uint64_t base_seed = ((uint64_t)blk0[1] << 32) | (uint64_t)blk0[0];
-        for (int j = 0; j < E; j++) env_seed[(size_t)k * E + j] = base_seed + (uint64_t)j;
-        const int32_t *sm = pod_seat_model + (size_t)k * P;
-        int32_t *sl = &slot_model[(size_t)k * P];
-        int nslot = 0;
-        for (int p = 0; p < P; p++) {
-            int at = 0;
-            while (at < nslot && sl[at] != sm[p]) at++;
-            if (at == nslot) sl[nslot++] = sm[p];
-            seat_slot[(size_t)k * P + p] = at;
-        }
-    }
-
-    const std::vector<int32_t> perms = generate_permutations(P);
-    const int nperm = (int)(perms.size() / (size_t)P);
-    const size_t np = c->net.n_params;
-
-    EvalBuffers buf;
-    PodState s{};
-    int32_t *d_perm_tab = nullptr, *d_seat_model = nullptr, *d_seat_slot = nullptr, *d_slot_model = nullptr;
+    int32_t *d_perm_tab = nullptr, *d_seat_model = nullptr, *d_slot_model = nullptr;
     float *d_params = nullptr, *d_oxc = nullptr, *d_ologits = nullptr;
     double *d_on = nullptr;
     EvalOutcome *d_sink = nullptr;
@@ -845,7 +526,6 @@ extern "C" bppo_status bppo_evaluate_pods(bppo_ctx *c, const bppo_eval_config *c
     const size_t ncount = (size_t)(K + 1) * n_pods;
     BPPO_HIP(c, buf.alloc(&d_perm_tab, perms.size()));
     BPPO_HIP(c, buf.alloc(&d_seat_model, (size_t)n_pods * P));
-    BPPO_HIP(c, buf.alloc(&d_seat_slot, (size_t)n_pods * P));
     BPPO_HIP(c, buf.alloc(&d_slot_model, (size_t)n_pods * P));
     BPPO_HIP(c, buf.alloc(&d_keys, (size_t)n_pods));
     BPPO_HIP(c, buf.alloc(&d_env_seed, (size_t)N));
@@ -855,7 +535,6 @@ extern "C" bppo_status bppo_evaluate_pods(bppo_ctx *c, const bppo_eval_config *c
     BPPO_HIP(c, buf.alloc(&s.group, (size_t)N));
     BPPO_HIP(c, buf.alloc(&s.gpos, (size_t)N));
     BPPO_HIP(c, buf.alloc(&s.didx, (size_t)N));
-    BPPO_HIP(c, buf.alloc(&s.slot, (size_t)N));
     BPPO_HIP(c, buf.alloc(&s.lrank, (size_t)N));
     BPPO_HIP(c, buf.alloc(&s.tempv, (size_t)N));
     BPPO_HIP(c, buf.alloc(&s.counts, ncount));
@@ -871,10 +550,10 @@ extern "C" bppo_status bppo_evaluate_pods(bppo_ctx *c, const bppo_eval_config *c
     BPPO_HIP(c, buf.alloc(&d_ologits, (size_t)N * A));
     BPPO_HIP(c, buf.alloc(&d_sink, (size_t)N));
     BPPO_HIP(c, buf.alloc(&d_games, (size_t)n_pods * cap));
-    BPPO_HIP(c, hipHostMalloc((void **)&buf.h_pod, sizeof(PodHdr)));
+    BPPO_HIP(c, hipHostMalloc((void **)&buf.h_hdr, sizeof(EvalHdr)));
     s.n_pods = n_pods; s.E = E; s.P = P; s.K = K; s.nperm = nperm; s.num_games = cfg->num_games; s.cap = cap;
     s.temp = bppo_eval::TempSched{cfg->temp_initial, cfg->temp_final, cfg->temp_cutoff, cfg->temp_decay};
-    s.perm_tab = d_perm_tab; s.seat_model = d_seat_model; s.seat_slot = d_seat_slot; s.slot_model = d_slot_model;
+    s.perm_tab = d_perm_tab; s.seat_model = d_seat_model; s.slot_model = d_slot_model;
     s.err = c->d_err;
 
     // models: uploads ordered on the context's stream, drained before the host arrays may go
@@ -893,38 +572,39 @@ extern "C" bppo_status bppo_evaluate_pods(bppo_ctx *c, const bppo_eval_config *c
     BPPO_HIP(c, hipMemcpyAsync(d_on, on.data(), sizeof(double) * on.size(), hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_perm_tab, perms.data(), sizeof(int32_t) * perms.size(), hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_seat_model, pod_seat_model, sizeof(int32_t) * (size_t)n_pods * P, hipMemcpyHostToDevice, c->stream));
-    BPPO_HIP(c, hipMemcpyAsync(d_seat_slot, seat_slot.data(), sizeof(int32_t) * seat_slot.size(), hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_slot_model, slot_model.data(), sizeof(int32_t) * slot_model.size(), hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_keys, keys.data(), sizeof(Key8) * keys.size(), hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_env_seed, env_seed.data(), sizeof(uint64_t) * env_seed.size(), hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemsetAsync(c->d_err, 0, 4, c->stream));
     BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
-    hipLaunchKernelGGL(k_pods_init, dim3(std::min((N + 255) / 256, 1024)), dim3(256), 0, c->stream, s, (uint64_t)2);
-    TRY(launch_check(c, "k_pods_init"));
-    // VecEnv::new and set_all_num_players per pod, as in bppo_evaluate, with env j of pod k = E::new(base_k + j)
+    hipLaunchKernelGGL(k_eval_init, dim3(std::min((N + 255) / 256, 1024)), dim3(256), 0, c->stream, s, (uint64_t)2);
+    TRY(launch_check(c, "k_eval_init"));
+    // per pod VecEnv::new (env j of pod k = E::new(base_k + j) and a reset), then set_all_num_players
+    // resets every env again (env.rs:281-302, 313-326); E::new's reward shaping is the zero schedule
+    // (liars_dice.rs:461-463, skull.rs:1062-1065); Skull is seated with the context's player_count
     BPPO_HIP(c, wide_env_reset(c->cfg.env_kind, c->stream, N, 0, P, c->d_wstate, c->d_env_pos, c->d_ep_ret, c->d_ep_len,
                                d_env_seed));
     BPPO_HIP(c, wide_env_reset_again(c->cfg.env_kind, c->stream, N, 0, c->d_wstate, c->d_env_pos, d_env_seed));
 
-    // a pod's block: its envs rounded up to whole waves, 256 threads at most (a thread then owns a run of envs)
-    const int pod_threads = std::min(EVP_POD_THREADS, (E + 63) / 64 * 64);
+    // a pod's block: its envs rounded up to whole waves, 1,024 threads at most (a thread then owns a run of envs)
+    const int pod_threads = std::min(EV_POD_THREADS, (E + 63) / 64 * 64);
     auto observe_group = [&]() -> bppo_status {
         BPPO_HIP(c, wide_env_observe(c->cfg.env_kind, c->G > 0, c->stream, N, c->d_wstate, c->d_bxc, c->d_bmask,
                                      c->d_bplayers));
-        hipLaunchKernelGGL(k_pods_group, dim3(n_pods), dim3(pod_threads), 0, c->stream, s, c->d_bplayers);
-        TRY(launch_check(c, "k_pods_group"));
-        hipLaunchKernelGGL(k_pods_scan, dim3(1), dim3(EVP_SCAN_THREADS), 0, c->stream, s);
-        TRY(launch_check(c, "k_pods_scan"));
-        BPPO_HIP(c, hipMemcpyAsync(buf.h_pod, s.hdr, sizeof(PodHdr), hipMemcpyDeviceToHost, c->stream));
+        hipLaunchKernelGGL(k_eval_group, dim3(n_pods), dim3(pod_threads), 0, c->stream, s, c->d_bplayers);
+        TRY(launch_check(c, "k_eval_group"));
+        hipLaunchKernelGGL(k_eval_scan, dim3(1), dim3(EV_SCAN_THREADS), 0, c->stream, s);
+        TRY(launch_check(c, "k_eval_scan"));
+        BPPO_HIP(c, hipMemcpyAsync(buf.h_hdr, s.hdr, sizeof(EvalHdr), hipMemcpyDeviceToHost, c->stream));
         BPPO_HIP(c, hipStreamSynchronize(c->stream));
         return BPPO_OK;
     };
     TRY(observe_group());
     bppo_status st = BPPO_OK;
     for (int step = 0;; step++) {
-        const PodHdr &h = *buf.h_pod;
+        const EvalHdr &h = *buf.h_hdr;
         if (h.unfinished == 0) break;              // every pod: num_games games or no active env (eval.rs:1670-1674)
-        if (step >= cfg->max_steps) { c->err = "evaluate_pods: max_steps exceeded before every pod had played num_games games"; st = BPPO_ERR_ARG; break; }
+        if (step >= cfg->max_steps) { c->err = who + ": max_steps exceeded before every pod had played num_games games"; st = BPPO_ERR_ARG; break; }
         const int32_t *gb = h.gbase;
         bool any_fwd = false;
         for (int k = 0; k < K; k++) any_fwd = any_fwd || (!((random_models >> k) & 1ull) && gb[k + 2] > gb[k + 1]);
@@ -941,9 +621,8 @@ extern "C" bppo_status bppo_evaluate_pods(bppo_ctx *c, const bppo_eval_config *c
         }
         EvalSampleArgs g;
         g.N = N; g.logits = c->d_logits; g.mask = c->d_bmask; g.group = s.group; g.didx = s.didx; g.temp = s.tempv;
-        g.random_models = 0; g.key = keys[0]; g.stream = 0; g.base = 0; g.dbase = nullptr;
+        g.random_models = random_models; g.pod_envs = E; g.pod_key = d_keys; g.pod_rngpos = s.rngpos; g.stream = 0;
         g.act = c->d_act_in; g.used = nullptr; g.err = c->d_err;
-        g.pod_envs = E; g.pod_key = d_keys; g.pod_rngpos = s.rngpos; g.random_models64 = random_models;
         BPPO_HIP(c, eval_sample(A, c->stream, g));
         WideStepArgs w;
         w.N = N; w.t = step; w.state = c->d_wstate; w.env_pos = c->d_env_pos; w.seed_base = 0;
@@ -953,30 +632,100 @@ extern "C" bppo_status bppo_evaluate_pods(bppo_ctx *c, const bppo_eval_config *c
         w.eps_cap = 0; w.err = c->d_err;
         w.frozen = s.frozen; w.sink = d_sink; w.env_seed = d_env_seed;
         BPPO_HIP(c, wide_env_step(c->cfg.env_kind, c->stream, w));
-        hipLaunchKernelGGL(k_pods_finish, dim3(n_pods), dim3(pod_threads), 0, c->stream, s, step, c->d_scr_d, d_sink,
+        hipLaunchKernelGGL(k_eval_finish, dim3(n_pods), dim3(pod_threads), 0, c->stream, s, step, c->d_scr_d, d_sink,
                            d_games);
-        TRY(launch_check(c, "k_pods_finish"));
+        TRY(launch_check(c, "k_eval_finish"));
         TRY(observe_group());
     }
-    // results: every pod's games, game count and RNG position; the episode counter back to zero
-    std::vector<bppo_eval_game> h_games((size_t)n_pods * cap);
-    std::vector<int32_t> h_ng((size_t)n_pods);
-    std::vector<uint64_t> h_pos((size_t)n_pods);
-    if (!h_games.empty())
-        BPPO_HIP(c, hipMemcpyAsync(h_games.data(), d_games, sizeof(bppo_eval_game) * h_games.size(), hipMemcpyDeviceToHost, c->stream));
-    BPPO_HIP(c, hipMemcpyAsync(h_ng.data(), s.games, sizeof(int32_t) * (size_t)n_pods, hipMemcpyDeviceToHost, c->stream));
-    BPPO_HIP(c, hipMemcpyAsync(h_pos.data(), s.rngpos, sizeof(uint64_t) * (size_t)n_pods, hipMemcpyDeviceToHost, c->stream));
+    // results, also after a max_steps error: every pod's game count and RNG position, then its
+    // games; the episode counter back to zero
+    BPPO_HIP(c, hipMemcpyAsync(n_games, s.games, sizeof(int32_t) * (size_t)n_pods, hipMemcpyDeviceToHost, c->stream));
+    if (rng_word_pos)
+        BPPO_HIP(c, hipMemcpyAsync(rng_word_pos, s.rngpos, sizeof(uint64_t) * (size_t)n_pods, hipMemcpyDeviceToHost, c->stream));
     BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
     BPPO_HIP(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < n_pods; k++) {
-        n_games[k] = h_ng[k];
-        if (rng_word_pos) rng_word_pos[k] = h_pos[k];
-        const int ng = std::min<int>(h_ng[k], cap);
-        if (ng > 0) std::memcpy(games + (size_t)k * cap_per_pod, &h_games[(size_t)k * cap], sizeof(bppo_eval_game) * (size_t)ng);
+    // pod k's played games go to games[k cap_per_pod ...] and nothing else is written there.  On
+    // the device the pods are cap apart, so one copy stages them all; a lone pod's need no staging
+    std::vector<bppo_eval_game> h_games(n_pods > 1 ? (size_t)n_pods * cap : 0);
+    const size_t ncopy = n_pods > 1 ? h_games.size() : (size_t)std::min<int>(n_games[0], cap);
+    if (ncopy > 0) {
+        BPPO_HIP(c, hipMemcpyAsync(n_pods > 1 ? h_games.data() : games, d_games, sizeof(bppo_eval_game) * ncopy,
+                                   hipMemcpyDeviceToHost, c->stream));
+        BPPO_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    for (size_t k = 0; k * cap < h_games.size(); k++) {
+        const int ng = std::min<int>(n_games[k], cap);
+        if (ng > 0) std::memcpy(games + k * cap_per_pod, &h_games[k * cap], sizeof(bppo_eval_game) * (size_t)ng);
     }
     if (st != BPPO_OK) return st;
-    const int32_t err = buf.h_pod->err;
-    if (err & 8) { c->err = "evaluate_pods: an action outside the env's action mask"; return BPPO_ERR_ARG; }
-    if (err & EV_ERR_ZERO_SUM) { c->err = "evaluate_pods: the sampler's softmax sum was zero"; return BPPO_ERR_NONFINITE; }
+    const int32_t err = buf.h_hdr->err;
+    if (err & 8) { c->err = who + ": an action outside the env's action mask"; return BPPO_ERR_ARG; }
+    if (err & EV_ERR_ZERO_SUM) { c->err = who + ": the sampler's softmax sum was zero"; return BPPO_ERR_NONFINITE; }
     return BPPO_OK;
+}
+
+// One pod of all the context's envs, seeded with cfg->seed, drawing over the seated models in
+// ascending model index (eval.rs:1685-1769).
+extern "C" bppo_status bppo_evaluate(bppo_ctx *c, const bppo_eval_config *cfg, int32_t n_models, const float *params,
+                                     const double *norm_mean, const double *norm_m2, const double *norm_count,
+                                     const int32_t *is_random, const int32_t *seat_model, int32_t n_checkpoints,
+                                     bppo_eval_game *games, int32_t cap, int32_t *n_games, uint64_t *rng_word_pos) {
+    if (!c) return BPPO_ERR_ARG;
+    if (!c->wide || c->cfg.env_kind == BPPO_ENV_CARTPOLE) {
+        c->err = "evaluate: multi-player envs only (no stats mode for CartPole)";
+        return BPPO_ERR_UNSUPPORTED;
+    }
+    if (!cfg || !seat_model || !n_games || (cap > 0 && !games) || cap < 0) { c->err = "evaluate: NULL argument"; return BPPO_ERR_ARG; }
+    if (cfg->num_games < 0 || cfg->max_steps < 0) { c->err = "evaluate: num_games and max_steps must not be negative"; return BPPO_ERR_ARG; }
+    if (n_models < 1 || n_models > EV_SINGLE_MAX_MODELS) { c->err = "evaluate: 1..15 models"; return BPPO_ERR_ARG; }
+    const int P = c->Pa, K = n_models;
+    // the reference's permutations are over 0..num_players and a further checkpoint panics
+    // (eval.rs:1801-1804), fewer fail its assert (:1640-1643)
+    if (n_checkpoints != P) { c->err = "evaluate: n_checkpoints must equal the seated player count"; return BPPO_ERR_ARG; }
+    const uint64_t random_models = random_mask(is_random, K);
+    for (int p = 0; p < P; p++)
+        if (seat_model[p] < 0 || seat_model[p] >= K) { c->err = "evaluate: seat_model names a model out of range"; return BPPO_ERR_ARG; }
+    if (random_models != (1ull << K) - 1ull && !params) { c->err = "evaluate: model parameters required"; return BPPO_ERR_ARG; }
+    std::vector<int32_t> slot_model((size_t)P, -1);
+    pod_slots(seat_model, P, true, slot_model.data());
+    const uint64_t seed = cfg->seed;
+    return evaluate_run(c, "evaluate", cfg, K, params, norm_mean, norm_m2, norm_count, random_models, 1, c->N, &seed,
+                        seat_model, slot_model, games, cap, n_games, rng_word_pos);
+}
+
+// The pods draw over their models in first-appearance order of their seats (run_pod's
+// de-duplication, tournament.rs:1811-1838).
+extern "C" bppo_status bppo_evaluate_pods(bppo_ctx *c, const bppo_eval_config *cfg, int32_t n_models, const float *params,
+                                          const double *norm_mean, const double *norm_m2, const double *norm_count,
+                                          const int32_t *is_random, int32_t n_pods, int32_t envs_per_pod,
+                                          const uint64_t *pod_seeds, const int32_t *pod_seat_model,
+                                          bppo_eval_game *games, int32_t cap_per_pod, int32_t *n_games,
+                                          uint64_t *rng_word_pos) {
+    if (!c) return BPPO_ERR_ARG;
+    if (!c->wide || c->cfg.env_kind == BPPO_ENV_CARTPOLE) {
+        c->err = "evaluate_pods: multi-player envs only (no stats mode for CartPole)";
+        return BPPO_ERR_UNSUPPORTED;
+    }
+    if (!cfg || !pod_seeds || !pod_seat_model || !n_games || (cap_per_pod > 0 && !games) || cap_per_pod < 0) {
+        c->err = "evaluate_pods: NULL argument";
+        return BPPO_ERR_ARG;
+    }
+    if (cfg->num_games < 0 || cfg->max_steps < 0) { c->err = "evaluate_pods: num_games and max_steps must not be negative"; return BPPO_ERR_ARG; }
+    if (n_models < 1 || n_models > EV_MAX_MODELS) { c->err = "evaluate_pods: 1..64 models"; return BPPO_ERR_ARG; }
+    if (n_pods < 1 || n_pods > EV_MAX_PODS) { c->err = "evaluate_pods: 1..1024 pods"; return BPPO_ERR_ARG; }
+    const int P = c->Pa, K = n_models, E = envs_per_pod;
+    if (E < 1 || (int64_t)n_pods * E != (int64_t)c->N) {
+        c->err = "evaluate_pods: n_pods * envs_per_pod must equal the context's num_envs";
+        return BPPO_ERR_ARG;
+    }
+    const uint64_t random_models = random_mask(is_random, K);
+    for (int i = 0; i < n_pods * P; i++)
+        if (pod_seat_model[i] < 0 || pod_seat_model[i] >= K) { c->err = "evaluate_pods: pod_seat_model names a model out of range"; return BPPO_ERR_ARG; }
+    const uint64_t all_models = K == 64 ? ~0ull : (1ull << K) - 1ull;
+    if (random_models != all_models && !params) { c->err = "evaluate_pods: model parameters required"; return BPPO_ERR_ARG; }
+    std::vector<int32_t> slot_model((size_t)n_pods * P, -1);
+    for (int k = 0; k < n_pods; k++)
+        pod_slots(pod_seat_model + (size_t)k * P, P, false, &slot_model[(size_t)k * P]);
+    return evaluate_run(c, "evaluate_pods", cfg, K, params, norm_mean, norm_m2, norm_count, random_models, n_pods, E,
+                        pod_seeds, pod_seat_model, slot_model, games, cap_per_pod, n_games, rng_word_pos);
 }

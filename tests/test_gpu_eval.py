@@ -59,7 +59,13 @@ CASES = {
     "skull_3": ("skull", "mlp", 24, 3, 40, (1.0, 0.0, None, False), [31, 32], [1], [0, 1, 0], 106),
     "skull_6": ("skull", "mlp", 8, 6, 10, (1.0, 0.0, None, False), [31, 32, None], [], [0, 1, 2, 0, 1, 0], 107),
     "c4_cnn": ("connect_four", "cnn", 16, 2, 20, (0.4, 0.0, 10, False), [41, 42], [], [0, 1], 108),
+    # seats that name the models out of ascending order, and a model that is not seated: the draws
+    # still go over the models in ascending index, not in the seats' first-appearance order
+    "c4_desc": ("connect_four", "mlp", 16, 2, 37, (0.4, 0.0, 10, False), [11, 12, 13], [], [2, 0], 109),
+    "ld_desc": ("liars_dice", "ctde", 35, 4, 60, (1.0, 0.2, 6, True), [21, None, 22], [2], [2, 0, 2, 1], 110),
 }
+# case: (steps, longest game, final word position) of the reference run
+DESC_RUNS = {"c4_desc": (50, 23, 368), "ld_desc": (65, 37, 1640)}
 
 
 def _models(name):
@@ -76,15 +82,19 @@ def _models(name):
 _refs = {}
 
 
-def reference(name):
-    if name not in _refs:
+def reference(name, order=None):
+    """order: the seated models listed in another order than ascending index (the seats renumbered to match)"""
+    key = (name, None if order is None else tuple(order))
+    if key not in _refs:
         env, net, N, P, games, sched, seeds, normed, seat_model, seed = CASES[name]
         cfg, params, norms = _models(name)
         d = _desc(env, net)
         models = [R.Model.random() if p is None else R.Model(d, p, norms[k]) for k, p in enumerate(params)]
-        _refs[name] = R.run_stats_mode(env, N, P, models, seat_model, games, R.TempSchedule(*sched), seed,
-                                       max_steps=MAX_STEPS)
-    return _refs[name]
+        if order is not None:
+            models, seat_model = [models[m] for m in order], [list(order).index(m) for m in seat_model]
+        _refs[key] = R.run_stats_mode(env, N, P, models, seat_model, games, R.TempSchedule(*sched), seed,
+                                      max_steps=MAX_STEPS)
+    return _refs[key]
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -97,6 +107,14 @@ def test_reference_run_ends_by_num_games(name):
         assert sorted(g[3] for g in out["games"]) == [11, 12, 13, 14, 15] and out["rng_pos"] == 2
     if name == "c4_mixed":          # the cap and the freeze rule fire in the last round
         assert len({g[5] for g in out["games"]}) > 1 and out["games"][-1][5] == out["steps"] - 1
+    if name in DESC_RUNS:
+        assert (out["steps"], out["max_len"], out["rng_pos"]) == DESC_RUNS[name]
+        # the draw-order rule: the seated models in first-appearance order of the seats play other games
+        seats = CASES[name][8]
+        first = reference(name, order=sorted(set(seats), key=seats.index))
+        assert [g[1:] for g in first["games"]] != [g[1:] for g in out["games"]]
+        if name == "ld_desc":
+            assert first["rng_pos"] == 1612
 
 
 def _device_run(name, max_steps=MAX_STEPS):
