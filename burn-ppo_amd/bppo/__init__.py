@@ -2,8 +2,8 @@
 
 Host mirror of the reference's surfaces over libbppo.so (include/bppo.h)."""
 from ._lib import BppoError, lib  # noqa: F401
-from .eval import (EvalStats, TempSchedule, evaluate, evaluate_pods, generate_permutations,  # noqa: F401
-                   rewards_to_placements)
+from .eval import (EvalStats, TempSchedule, evaluate, evaluate_checkpoints, evaluate_episodes,  # noqa: F401
+                   evaluate_pods, generate_permutations, rewards_to_placements)
 from .tournament import round_robin_pods, run_round, swiss_points  # noqa: F401
 from .host import make_config, minibatch_sizes, orthogonal_init, schedule_get  # noqa: F401
 from .ppo import (ActorCritic, Context, RolloutBuffer, Trainer, VecEnv, collect_rollouts,  # noqa: F401

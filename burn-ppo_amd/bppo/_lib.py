@@ -106,7 +106,7 @@ EXPORTS = (
     "bppo_set_explained_variance_mode", "bppo_set_minibatch_kernel", "bppo_set_rank",
     "bppo_debug_record_params",
     "bppo_evaluate", "bppo_eval_config_size", "bppo_eval_game_size", "bppo_debug_eval_sample",
-    "bppo_debug_eval_perms", "bppo_evaluate_pods",
+    "bppo_debug_eval_perms", "bppo_evaluate_pods", "bppo_evaluate_episodes",
     "bppo_opp_completion_size", "bppo_opponents_completions", "bppo_opponents_results",
 )
 
@@ -202,6 +202,8 @@ def lib():
                                 C.POINTER(i32), C.POINTER(u64)]),
         "bppo_evaluate_pods": (i32, [vp, C.POINTER(EvalConfig), i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32,
                                      vp, vp]),
+        "bppo_evaluate_episodes": (i32, [vp, C.POINTER(EvalConfig), i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp,
+                                         vp]),
         "bppo_debug_eval_sample": (i32, [i32, i32, i32, vp, vp, vp, u64, u64, u64, vp, vp]),
         "bppo_debug_eval_perms": (i32, [i32, vp]),
     }

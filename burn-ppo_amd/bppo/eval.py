@@ -5,10 +5,13 @@
     rewards_to_placements   eval.rs:276-306
     evaluate                eval.rs:1621-1877 run_stats_mode_env -> EvalStats (eval.rs:315-390)
     evaluate_pods           many such matchups in one device loop, one RNG seed per pod
+    evaluate_episodes       single-player stats mode (CartPole): pods of one checkpoint each in one
+                            kernel launch sequence -> EvalStats.reward_summary (eval.rs:416-469)
+    evaluate_checkpoints    checkpoint directories as the pods of one evaluate_episodes call
 
-The games run inside libbppo (bppo_evaluate, csrc/eval.hip) on a context of their
-own.  Checkpoint loading stays with bppo.checkpoint; ratings and printing are not
-part of this module."""
+The games run inside libbppo (bppo_evaluate, csrc/eval.hip; bppo_evaluate_episodes,
+csrc/eval_cartpole.hip) on a context of their own.  Checkpoint loading stays with
+bppo.checkpoint; ratings and printing are not part of this module."""
 import ctypes as C
 
 import numpy as np
@@ -149,6 +152,24 @@ class EvalStats:
     def draws(self):
         return sum(1 for o in self.game_outcomes if all(p == 1 for p in o))
 
+    def reward_summary(self):
+        """the numbers print_single_player_summary prints (eval.rs:416-469) for player 0, in f64:
+        mean, population std, min, max, p25 / p50 / p75 as sorted[len * q / 100] clamped to the last
+        index, and the episode lengths' mean / min / max.  None without reward data."""
+        rewards = sorted(float(r[0]) for r in self.game_rewards if len(r))
+        if not rewards:
+            return None
+        n = len(rewards)
+        mean = sum(rewards) / n
+        var = sum((r - mean) ** 2 for r in rewards) / n
+        out = dict(mean=mean, std=var ** 0.5, min=rewards[0], max=rewards[-1])
+        for q in (25, 50, 75):
+            out[f"p{q}"] = rewards[min(n * q // 100, n - 1)]
+        if self.episode_lengths:
+            out.update(length_mean=sum(self.episode_lengths) / len(self.episode_lengths),
+                       length_min=min(self.episode_lengths), length_max=max(self.episode_lengths))
+        return out
+
 
 def _pack_models(ctx, models, normalizers):
     """models[k]: a flat parameter vector or None (the random player); normalizers[k]:
@@ -214,6 +235,14 @@ def evaluate(config, models, normalizers, seat_model, num_games, temp_schedule=N
     player), every permutation of the seats in turn.  -> EvalStats"""
     if temp_schedule is None:
         temp_schedule = TempSchedule.env_default(config["env"])
+    if config["env"] == "cartpole":
+        # single-player stats mode: one pod of config["num_envs"] envs on the fused kernel
+        if [int(m) for m in seat_model] != [0]:
+            raise ValueError("CartPole has one player: seat_model must be [0]")
+        stats, = evaluate_episodes(config, [models[0]], [normalizers[0]] if normalizers else None, num_games,
+                                   config["num_envs"], temp_schedule, seeds=[seed], device=device,
+                                   max_steps=max_steps)
+        return stats
     ctx = Context(config, device=device)
     try:
         rec, pos = evaluate_ctx(ctx, models, normalizers, seat_model, num_games, temp_schedule, seed, max_steps)
@@ -271,3 +300,98 @@ def evaluate_pods(config, models, normalizers, pods, num_games, envs_per_pod, te
     finally:
         ctx.close()
     return [_stats(rec, pos, len(pods[k])) for k, (rec, pos) in enumerate(out)]
+
+
+def evaluate_episodes_ctx(ctx, models, normalizers, num_games, envs_per_pod, temp_schedule, seeds, max_steps=None,
+                          steps_per_launch=0):
+    """bppo_evaluate_episodes on an existing CartPole context, which is read for its net shape
+    and stream only (its envs, RNG, parameters and buffers are not touched).  Pod k plays num_games
+    episodes of models[k] (a flat parameter vector; normalizers[k]: (mean, m2, count) or None) on
+    envs_per_pod envs with StdRng(seeds[k]).  -> [(games as a numpy record array, rng word
+    position, loop iterations)] per pod"""
+    n_pods, cap = len(models), max(int(num_games), 1)
+    if any(m is None for m in models):
+        raise ValueError("single-player evaluation has no random player: every model needs parameters")
+    params, mean, m2, cnt, _ = _pack_models(ctx, models, normalizers)
+    pod_seeds = np.ascontiguousarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], np.uint64)
+    if len(pod_seeds) != n_pods:
+        raise ValueError("one seed per pod")
+    if max_steps is None:
+        # an episode lasts at most 500 steps and an env records at most ceil(num_games / envs) + 1
+        max_steps = 500 * (int(num_games) // max(int(envs_per_pod), 1) + 2)
+    cfg = _eval_config(num_games, envs_per_pod, temp_schedule, 0, max_steps)
+    games = (L.EvalGame * (cap * max(n_pods, 1)))()
+    n = np.zeros(max(n_pods, 1), np.int32)
+    pos = np.zeros(max(n_pods, 1), np.uint64)
+    steps = np.zeros(max(n_pods, 1), np.int32)
+    st = L.lib().bppo_evaluate_episodes(ctx.h, C.byref(cfg), n_pods, int(envs_per_pod), params.ctypes.data,
+                                        mean.ctypes.data, m2.ctypes.data, cnt.ctypes.data, pod_seeds.ctypes.data,
+                                        int(steps_per_launch), C.cast(games, C.c_void_p), cap, n.ctypes.data,
+                                        pos.ctypes.data, steps.ctypes.data)
+    L.check(st, ctx.h)
+    rec = np.frombuffer(games, dtype=np.dtype(L.EvalGame), count=cap * n_pods).copy().reshape(n_pods, cap)
+    return [(rec[k, :min(int(n[k]), int(num_games))], int(pos[k]), int(steps[k])) for k in range(n_pods)]
+
+
+def evaluate_episodes(config, models, normalizers, num_games, envs_per_pod, temp_schedule=None, seeds=None, seed=0,
+                      device=0, max_steps=None, steps_per_launch=0):
+    """Single-player stats mode (run_stats_mode_env with num_players = 1, eval.rs:1621-1877) for
+    CartPole: pod k plays num_games episodes of models[k] on envs_per_pod envs with its own RNG,
+    StdRng(seeds[k]) (default seed + k), all pods in one kernel launch sequence on a small
+    context of its own.  The default schedule is the trait's (0.3, no cutoff).  -> [EvalStats],
+    whose reward_summary() gives print_single_player_summary's numbers"""
+    if temp_schedule is None:
+        temp_schedule = TempSchedule.env_default(config["env"])
+    if seeds is None:
+        seeds = [seed + k for k in range(len(models))]
+    cfg = dict(config)
+    cfg.update(num_envs=8, num_steps=4, num_minibatches=1, num_epochs=1)   # the context lends its net shape only
+    ctx = Context(cfg, device=device)
+    try:
+        out = evaluate_episodes_ctx(ctx, models, normalizers, num_games, envs_per_pod, temp_schedule, seeds,
+                                    max_steps, steps_per_launch)
+    finally:
+        ctx.close()
+    return [_stats(rec, pos, 1) for rec, pos, _ in out]
+
+
+def evaluate_checkpoints(dirs, num_games, envs_per_pod, temp_schedule=None, seeds=None, seed=0, device=0,
+                         max_steps=None):
+    """Every checkpoint directory of a CartPole run (metadata.json, model.mpk and, when the run
+    normalized observations, normalizer.json; bppo.checkpoint) as one pod of a single
+    evaluate_episodes call.  The directories must describe one architecture.
+    -> ([EvalStats] per directory, index of the best mean return)"""
+    import json
+    import os
+
+    from . import checkpoint as ck
+    from .host import make_config
+    dirs = list(dirs)
+    if not dirs:
+        raise ValueError("no checkpoint directories")
+    metas = [ck.load_metadata(d) for d in dirs]
+
+    def arch(m):
+        return (m.env_name, m.network_type, m.hidden_size, m.num_hidden, m.activation, m.split_networks)
+
+    if any(arch(m) != arch(metas[0]) for m in metas):
+        raise ValueError("evaluate_checkpoints: the checkpoints differ in architecture")
+    m0 = metas[0]
+    if m0.env_name != "cartpole":
+        raise ValueError("evaluate_checkpoints: single-player (CartPole) checkpoints only")
+    config = make_config("cartpole", hidden_size=m0.hidden_size, num_hidden=m0.num_hidden, activation=m0.activation,
+                         network_type=m0.network_type, split_networks=m0.split_networks)
+    models = [ck.load_model(os.path.join(d, "model.mpk")) for d in dirs]
+    norms = []
+    for d in dirs:
+        p = os.path.join(d, "normalizer.json")
+        if os.path.exists(p):
+            with open(p) as f:
+                j = json.load(f)
+            norms.append((np.asarray(j["mean"], np.float64), np.asarray(j["var"], np.float64), float(j["count"])))
+        else:
+            norms.append(None)
+    stats = evaluate_episodes(config, models, norms, num_games, envs_per_pod, temp_schedule, seeds, seed, device,
+                              max_steps)
+    means = [s.reward_summary()["mean"] if s.total_games else float("-inf") for s in stats]
+    return stats, int(np.argmax(means))

@@ -40,6 +40,7 @@
 #include "bppo_envs.h"
 #include "bppo_wide.h"
 #include "bppo_eval.h"
+#include "bppo_scan.h"
 
 namespace bppo {
 
@@ -74,28 +75,6 @@ struct EvalState {
     EvalHdr *hdr;
     const int32_t *err;
 };
-
-// exclusive scan of a (rows, draws) pair packed in 64 bits over the block's threads in
-// thread order; *total = the block's sum.  wsum: one slot per wave.
-__device__ __forceinline__ uint64_t block_scan_excl(uint64_t v, uint64_t *wsum, uint64_t *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint64_t inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t o = (uint64_t)__shfl_up((unsigned long long)inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    __syncthreads();               // the previous scan's readers are done with wsum
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint64_t base = 0, tot = 0;
-    for (int i = 0; i < nw; i++) {
-        const uint64_t s = wsum[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    *total = tot;
-    return base + inc - v;
-}
 
 struct EvalSampleArgs {
     int N;

@@ -13,36 +13,6 @@
 
 namespace bppo {
 
-// ObsNormalizer::normalize_batch (normalization.rs:58-75) from device stats
-// on = {mean[D], M2[D], count}.  The stats are fixed for a whole rollout, so
-// the per-dim std is derived once (same f64 ops as per call) and each step only
-// does (raw - mean) / sd.
-struct ObsNorm5 {
-    double mean[5], sd[5];
-    bool on;
-    __device__ __forceinline__ void load(const double *__restrict__ st, int norm_on) {
-        const double cnt = st[10];
-        on = norm_on && cnt >= 2.0;
-#pragma unroll
-        for (int d = 0; d < 5; d++) {
-            const double var = st[5 + d] / cnt;
-            double s = sqrt(var);
-            sd[d] = s < 1e-8 ? 1e-8 : s;
-            mean[d] = st[d];
-        }
-    }
-    __device__ __forceinline__ void apply(const float (&raw)[5], float (&out)[5]) const {
-#pragma unroll
-        for (int d = 0; d < 5; d++) {
-            if (!on) { out[d] = raw[d]; continue; }
-            float z = (float)(((double)raw[d] - mean[d]) / sd[d]);
-            z = z < -10.0f ? -10.0f : z;
-            z = z > 10.0f ? 10.0f : z;
-            out[d] = z;
-        }
-    }
-};
-
 // per-env raw-observation statistics of one rollout (count T) for the
 // normalizer update (normalization.rs:37-53): sums shifted by the first
 // observation, no division per step; mean / M2 at the end match the

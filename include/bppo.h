@@ -401,6 +401,48 @@ bppo_status bppo_evaluate_pods(bppo_ctx *ctx, const bppo_eval_config *cfg, int32
                                const uint64_t *pod_seeds, const int32_t *pod_seat_model, bppo_eval_game *games,
                                int32_t cap_per_pod, int32_t *n_games, uint64_t *rng_word_pos);
 
+/* Single-player stats mode: run_stats_mode_env::<CartPole> (eval.rs:1621-1877) with one
+ * checkpoint, n_pods times in one launch sequence; its summary is
+ * EvalStats::print_single_player_summary (eval.rs:416-469).  Pod k plays cfg->num_games episodes
+ * of params[k] on envs_per_pod envs with its own StdRng(pod_seeds[k]); cfg->seed is not read.
+ * One thread block plays a whole pod (csrc/eval_cartpole.hip), so a single pod uses one CU and
+ * the GPU fills through pods: every checkpoint of a run, or one checkpoint under many seeds.
+ * Contexts: CartPole with a net the fused kernels cover (hidden {16, 32, 64} x {1, 2} layers,
+ * relu or tanh, no split_networks).  Any other CartPole net: BPPO_ERR_UNSUPPORTED; any other
+ * env: BPPO_ERR_UNSUPPORTED (those are bppo_evaluate's and bppo_evaluate_pods').
+ *   n_pods 1..1024; envs_per_pod 1..16384, independent of the context's num_envs;
+ *   params [n_pods][n_params] of the context's net; norm_mean / norm_m2 [n_pods][5], norm_count
+ *   [n_pods]: any NULL array, or count < 2, = raw observations (eval.rs:1727-1734);
+ *   steps_per_launch: loop iterations per kernel launch, 0 = the default (256 / envs per
+ *   thread, at least 1: a launch of about 20 ms or less); results do not depend on it.
+ * Semantics per pod:
+ *   RNG StdRng(pod_seeds[k]); base = its first u64, words 0 and 1 (eval.rs:1646-1648); env j =
+ *   CartPole::new(base + j), reset again by VecEnv::new and by set_all_num_players (cartpole.rs:104,
+ *   env.rs:289-293, 313-326): three resets from the env's own stream; draws follow from word 2;
+ *   per iteration, while games < num_games and an env is active (eval.rs:1670-1674): every
+ *   active env in env order samples at TempSchedule::get_temp of its move count with no mask
+ *   (eval.rs:1766, 223-272; the argmax takes the last of equal maxima; one word per draw, none at
+ *   temperature 0), steps, and on done records {total, length} and resets from its own stream
+ *   (env.rs:400-487); move counts advance for every env, frozen ones included (eval.rs:1775-1777);
+ *   finished episodes are recorded in env order up to num_games (eval.rs:1783-1831):
+ *   total_reward[0] the total, placement[0] = 1, other slots 0, length, env_index within the
+ *   pod, perm_index 0, step the iteration; a recorded env's move count returns to 0, an episode
+ *   past the cap is dropped; then the freeze rule (eval.rs:1839-1869).
+ *   games [n_pods][cap_per_pod], n_games [n_pods], rng_word_pos [n_pods] (nullable),
+ *   loop_steps [n_pods] (nullable): the iterations the pod ran.  num_games = 0 runs no
+ *   iteration and leaves position 2.
+ * A pod unfinished after cfg->max_steps iterations: BPPO_ERR_ARG ("max_steps"); n_games,
+ * rng_word_pos, loop_steps and the games so far are still written.
+ * The call reads the context for the net shape, activation, stream and error slot only: its
+ * VecEnv, RNG, parameters, optimizer, normalizers, rollout buffers and a pipelined prefetched
+ * rollout are not touched (unlike bppo_evaluate, which resets the VecEnv).  All device memory of
+ * the call is allocated by it and freed when it ends. */
+bppo_status bppo_evaluate_episodes(bppo_ctx *ctx, const bppo_eval_config *cfg, int32_t n_pods, int32_t envs_per_pod,
+                                   const float *params, const double *norm_mean, const double *norm_m2,
+                                   const double *norm_count, const uint64_t *pod_seeds, int32_t steps_per_launch,
+                                   bppo_eval_game *games, int32_t cap_per_pod, int32_t *n_games,
+                                   uint64_t *rng_word_pos, int32_t *loop_steps);
+
 /* parity hooks: export / import a RolloutBuffer field.  names: "obs", "priv",
  * "actions" (i32), "rewards", "dones", "values", "log_probs", "advantages",
  * "returns", "players" (i32), "all_rewards", "masks", "last_v_pp", "perm" (u32,
