@@ -72,6 +72,18 @@ class OppCompletion(C.Structure):
                 ("position_to_opponent", C.c_int32 * MAX_PLAYERS)]
 
 
+class PlConfig(C.Structure):
+    """bppo_pl_config: PlackettLuceConfig (plackett_luce.rs:102-127) + the backend switch"""
+    _fields_ = [("max_iterations", C.c_int32), ("backend", C.c_int32), ("convergence_threshold", C.c_double),
+                ("epsilon", C.c_double), ("anchor_elo", C.c_double), ("ci_inflation_factor", C.c_double)]
+
+
+class PlStats(C.Structure):
+    """bppo_pl_stats: RatingStats (plackett_luce.rs:80-89) + the table's size"""
+    _fields_ = [("converged", C.c_int32), ("iterations_used", C.c_int32), ("final_delta", C.c_double),
+                ("fit_ms", C.c_double), ("n_games", C.c_int64), ("n_comparisons", C.c_int64)]
+
+
 METRIC_NAMES = ("policy_loss", "value_loss", "entropy", "entropy_scaled", "approx_kl", "clip_fraction",
                 "explained_variance", "total_loss", "value_mean", "returns_mean", "adv_mean_raw",
                 "adv_std_raw", "adv_min_raw", "adv_max_raw", "value_error_mean", "value_error_std",
@@ -108,13 +120,18 @@ EXPORTS = (
     "bppo_evaluate", "bppo_eval_config_size", "bppo_eval_game_size", "bppo_debug_eval_sample",
     "bppo_debug_eval_perms", "bppo_evaluate_pods", "bppo_evaluate_episodes",
     "bppo_opp_completion_size", "bppo_opponents_completions", "bppo_opponents_results",
+    "bppo_ratings_create", "bppo_ratings_destroy", "bppo_ratings_last_error", "bppo_ratings_clear",
+    "bppo_ratings_add_games", "bppo_ratings_add_completions", "bppo_ratings_num_games", "bppo_ratings_fit",
+    "bppo_ratings_last_fit_phases",
+    "bppo_pl_config_size", "bppo_pl_stats_size",
 )
 
 # ABI struct -> the library's sizeof export (checked when the library loads)
 STRUCT_SIZES = {"bppo_config_size": Config, "bppo_update_metrics_size": UpdateMetrics,
                 "bppo_episode_size": Episode, "bppo_rollout_info_size": RolloutInfo,
                 "bppo_eval_config_size": EvalConfig, "bppo_eval_game_size": EvalGame,
-                "bppo_opp_completion_size": OppCompletion}
+                "bppo_opp_completion_size": OppCompletion,
+                "bppo_pl_config_size": PlConfig, "bppo_pl_stats_size": PlStats}
 
 _lib = None
 
@@ -206,6 +223,15 @@ def lib():
                                          vp]),
         "bppo_debug_eval_sample": (i32, [i32, i32, i32, vp, vp, vp, u64, u64, u64, vp, vp]),
         "bppo_debug_eval_perms": (i32, [i32, vp]),
+        "bppo_ratings_create": (i32, [C.c_int, vp, C.POINTER(vp)]),
+        "bppo_ratings_destroy": (None, [vp]),
+        "bppo_ratings_last_error": (C.c_char_p, [vp]),
+        "bppo_ratings_clear": (i32, [vp]),
+        "bppo_ratings_add_games": (i32, [vp, C.c_int64, i32, vp, vp, vp]),
+        "bppo_ratings_add_completions": (i32, [vp, vp, i32, vp, i32, C.POINTER(C.c_int64)]),
+        "bppo_ratings_num_games": (i32, [vp, C.POINTER(C.c_int64)]),
+        "bppo_ratings_last_fit_phases": (i32, [vp, vp]),
+        "bppo_ratings_fit": (i32, [vp, C.POINTER(PlConfig), i32, i32, vp, vp, vp, C.POINTER(PlStats)]),
     }
     for name in STRUCT_SIZES:
         sig[name] = (sz, [])

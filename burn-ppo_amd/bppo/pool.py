@@ -11,6 +11,10 @@ queue_game_result per device model slot, come back through bppo_opponents_comple
 bppo_opponents_results (Context.opponent_completions / opponent_results).  PoolTrainer
 keeps the device's model slots (at most 15) equal to the pool members in use and runs
 one training iteration per step.  One context only: at W > 1 each rank keeps its own sums.
+
+RatingHistory (rating_history.rs:78-341 without the files) keeps every rated game of a run in
+a device rating table (bppo.ratings) and refits it on demand; PoolTrainer(rating_history=...)
+feeds it each rollout's finished games without taking them through the host.
 """
 import json
 import os
@@ -21,6 +25,7 @@ import numpy as np
 from .checkpoint import to_json_pretty
 from .host import schedule_get
 from .ppo import Trainer, train_step
+from .ratings import PlackettLuceConfig, RatingTable
 from .rng import StdRng
 
 MAX_DEVICE_MODELS = 15
@@ -218,17 +223,105 @@ class OpponentPool:
         return doc["config"]
 
 
+class RatingHistory:
+    """rating_history.rs:78-341 without the persistence and the graph: the games live in a
+    rating table; player ids are the order of registration (ensure_checkpoint_registered)."""
+
+    def __init__(self, device=0, backend=None):
+        self.table = RatingTable(device=device)
+        self.backend = backend or ("host" if device is None else "device")
+        self.checkpoint_to_idx = {}
+        self.idx_to_checkpoint = []
+        self.idx_to_step = []
+        self.first_checkpoint_idx = None
+        self._current = None
+        self.cached_ratings = None
+        self.last_result = None
+
+    def ensure_checkpoint_registered(self, name, step=0):
+        idx = self.checkpoint_to_idx.get(name)
+        if idx is not None:
+            if step > 0 and self.idx_to_step[idx] == 0:
+                self.idx_to_step[idx] = int(step)
+            return idx
+        idx = len(self.idx_to_checkpoint)
+        self.checkpoint_to_idx[name] = idx
+        self.idx_to_checkpoint.append(name)
+        self.idx_to_step.append(int(step))
+        return idx
+
+    def on_checkpoint_saved(self, name, step):
+        idx = self.ensure_checkpoint_registered(name, step)
+        if self.first_checkpoint_idx is None:
+            self.first_checkpoint_idx = idx
+        self.idx_to_step[idx] = int(step)
+        self._current = name
+        self.cached_ratings = None
+
+    @property
+    def current_checkpoint(self):
+        return self._current
+
+    @property
+    def total_games(self):
+        return self.table.num_games
+
+    def record_game(self, current, opponents, placements):
+        """placements: [the learner's, then each opponent's] (rating_placements, ppo.rs:890-897)"""
+        ids = [self.ensure_checkpoint_registered(current)] + [self.ensure_checkpoint_registered(o) for o in opponents]
+        self.table.add_games([ids], [list(placements)])
+        self.cached_ratings = None
+
+    def record_rollout(self, ctx, slot_to_pool, pool):
+        """main.rs:755-790 for every finished opponent game of ctx's last rollout, on the device:
+        the learner plays under the current checkpoint's name ("step_00000000" before the first
+        save), device model slot k under pool member slot_to_pool[k]'s; games against nothing but
+        the current checkpoint are skipped.  The learner and every slot's checkpoint are
+        registered, whether or not they finished a game.  -> games recorded"""
+        learner = self.ensure_checkpoint_registered(self._current or "step_00000000")
+        slots = [self.ensure_checkpoint_registered(pool.get_checkpoint_name(i)) for i in slot_to_pool]
+        added = self.table.add_completions(ctx, learner, slots)
+        if added:
+            self.cached_ratings = None
+        return added
+
+    def compute_ratings(self):
+        """rating_history.rs:270-341 -> {current_elo, best_elo, best_step, total_games}"""
+        n = len(self.idx_to_checkpoint)
+        total = self.total_games
+        if n == 0 or total == 0:
+            self.cached_ratings = []
+            return dict(current_elo=1000.0, best_elo=1000.0, best_step=0, total_games=0)
+        res = self.table.fit(n, 0, PlackettLuceConfig(), self.backend)
+        self.last_result = res
+        raw = [r.rating for r in res.ratings]
+        first = self.first_checkpoint_idx if self.first_checkpoint_idx is not None else 0
+        shift = 1000.0 - (raw[first] if first < n else 1000.0)
+        adjusted = [r + shift for r in raw]
+        best_idx, best = 0, -np.inf
+        for i, r in enumerate(adjusted):
+            if r > best:
+                best, best_idx = r, i
+        cur = max(n - 2, 0)
+        self.cached_ratings = adjusted
+        return dict(current_elo=adjusted[cur], best_elo=best, best_step=self.idx_to_step[best_idx], total_games=total)
+
+    def close(self):
+        self.table.close()
+
+
 class PoolTrainer:
     """The opponent-pool branch of run_training's loop (main.rs:616-654, 729-803) on one
     context: envs [0, num_opponent_envs) play the pool's current opponents, the finished
     games' results feed the pool's win rates, and the opponents are re-drawn every update."""
 
-    def __init__(self, cfg, pool, num_opponent_envs, device=0, params=None, init_seed=0):
+    def __init__(self, cfg, pool, num_opponent_envs, device=0, params=None, init_seed=0, rating_history=None):
         if not pool.has_opponents():
             raise ValueError("PoolTrainer: the pool has no checkpoints")
         self.trainer = Trainer(cfg, device=device, params=params, init_seed=init_seed)
         self.ctx = self.trainer.ctx
         self.pool = pool
+        self.rating_history = rating_history     # a RatingHistory fed by step() and add_checkpoint()
         self.n_opp = int(num_opponent_envs)
         P = self.ctx.seats
         if pool.num_opponent_slots != P - 1:
@@ -279,6 +372,8 @@ class PoolTrainer:
     def add_checkpoint(self, name, step, normalizer=None):
         """the learner's current parameters join the pool (main.rs: after a checkpoint save)"""
         self.pool.add_checkpoint(name, step, self.trainer.model.get_params(), normalizer)
+        if self.rating_history is not None:
+            self.rating_history.on_checkpoint_saved(name, step)
 
     def step(self):
         """one update: rollout against the current opponents, GAE, PPO update, then
@@ -296,6 +391,8 @@ class PoolTrainer:
         self.pool_performance = self.pool.get_pool_performance(self.ctx.num_players)
         self.pool.refresh_current_opponents()
         self.history.append(list(self.pool.current_opponents))
+        if self.rating_history is not None:      # before the re-upload empties the records
+            metrics["rated_games"] = self.rating_history.record_rollout(self.ctx, self.slot_to_pool, self.pool)
         # the seats stay as the rollout left them; only the slot numbering may change
         lp, p2o = self.ctx.opponent_envs()
         self.learner_pos = lp.copy()

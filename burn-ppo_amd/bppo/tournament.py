@@ -5,11 +5,17 @@
     run_round               the pods of a round through bppo.eval.evaluate_pods; per pod the
                             MatchupGames content of run_pod (tournament.rs:1788-1870)
 
+    find_anchor_index       tournament.rs:1017-1033
+    rate_round              compute_ratings(contestants, all_games), tournament.rs:1035-1049, on a
+                            device rating table (bppo.ratings)
+
 Every pod of a round has its own RNG (evaluate_pods), where the reference hands one StdRng
-from pod to pod.  Pairing for Swiss rounds, ratings and graphs are not part of this module."""
+from pod to pod.  Pairing for Swiss rounds (swiss_pods, form_dutch_pods*), the graphs and
+checkpoint discovery on disk are not part of this module."""
 import itertools
 
 from .eval import evaluate_pods
+from .ratings import RatingTable
 
 
 def round_robin_pods(n, pod_size):
@@ -40,3 +46,46 @@ def run_round(config, models, normalizers, pods, num_games, envs_per_pod, temp_s
                           device, max_steps)
     return [{"contestants": list(pod), "games": [list(o) for o in st.game_outcomes], "stats": st}
             for pod, st in zip(pods, stats)]
+
+
+def find_anchor_index(names):
+    """the anchor of a tournament's ratings: the contestant called "Random" if there is one, else
+    the "step_*" contestant with the smallest name (the first of equal ones), else None"""
+    for i, n in enumerate(names):
+        if n == "Random":
+            return i
+    best = None
+    for i, n in enumerate(names):
+        if n.startswith("step_") and (best is None or n < names[best]):
+            best = i
+    return best
+
+
+def rate_round(results, n_contestants, anchor, table=None, random_index=None, config=None, device=0,
+               backend="device"):
+    """Append the games of run_round's output to a rating table and fit it over n_contestants
+    players: a pod's contestant indices are the player ids as they are; a None contestant (the
+    random player) is player random_index, as the caller numbers it.  table: a RatingTable that
+    already holds the earlier rounds' games (the reference refits over all games after every
+    round, tournament.rs:2250); None = a table of this call's own.  -> RatingResult"""
+    own = table is None
+    if own:
+        table = RatingTable(device=device)
+    try:
+        players, placements = [], []
+        for pod in results:
+            ids = []
+            for c in pod["contestants"]:
+                if c is None:
+                    if random_index is None:
+                        raise ValueError("rate_round: a pod seats the random player (None); give random_index")
+                    c = random_index
+                ids.append(int(c))
+            for game in pod["games"]:
+                players.append(ids)
+                placements.append([int(p) for p in game])
+        table.add_games(players, placements)
+        return table.fit(n_contestants, anchor, config, backend)
+    finally:
+        if own:
+            table.close()

@@ -443,6 +443,60 @@ bppo_status bppo_evaluate_episodes(bppo_ctx *ctx, const bppo_eval_config *cfg, i
                                    bppo_eval_game *games, int32_t cap_per_pod, int32_t *n_games,
                                    uint64_t *rng_word_pos, int32_t *loop_steps);
 
+/* ---- Plackett-Luce ratings (plackett_luce.rs) ----------------------------- */
+/* A rating table is an object of its own, not part of a context: a tournament's or a training
+ * run's ratings outlive any one evaluation context.  Games and their expanded comparisons stay in
+ * device memory between calls; a fit only iterates.  Not thread-safe. */
+typedef struct {            /* PlackettLuceConfig, plackett_luce.rs:102-127 */
+    int32_t max_iterations;  /* 100 */
+    int32_t backend;         /* 0 = device, 1 = host: the reference's arithmetic in its order */
+    double convergence_threshold, epsilon, anchor_elo, ci_inflation_factor;  /* 1e-6, 1e-10, 1000, 1.3 */
+} bppo_pl_config;
+typedef struct {            /* RatingStats, plackett_luce.rs:80-89 */
+    int32_t converged, iterations_used;
+    double final_delta;
+    double fit_ms;           /* wall time of the call */
+    int64_t n_games, n_comparisons;
+} bppo_pl_stats;
+typedef struct bppo_ratings bppo_ratings;
+
+/* hip_device = -1: a host-only table (no GPU is touched; only backend 1 fits it).  hip_stream may
+ * be NULL (the table creates its own). */
+bppo_status bppo_ratings_create(int hip_device, void *hip_stream, bppo_ratings **out);
+void        bppo_ratings_destroy(bppo_ratings *r);
+const char *bppo_ratings_last_error(const bppo_ratings *r);
+bppo_status bppo_ratings_clear(bppo_ratings *r);
+/* append n games of at most P (1..6) players: players [n][P] (player ids >= 0, -1 pads a shorter
+ * game at its end), placements [n][P] (1 = first, ties share; ignored where players is -1),
+ * weight [n] or NULL (= 1): a game listed once with weight w counts as w identical games.
+ * BPPO_ERR_ARG (nothing is appended): P outside 1..6, an id < -1, an id after a -1 in its row,
+ * a placement < 1, a non-finite or non-positive weight. */
+bppo_status bppo_ratings_add_games(bppo_ratings *r, int64_t n, int32_t P, const int32_t *players,
+                                   const int32_t *placements, const double *weight);
+/* append the kept opponent completions of ctx's last rollout straight from the device records
+ * (main.rs:755-790): game = [learner_player, slot_to_player[position_to_opponent[seat]] for the
+ * opponent seats in seat order], placements = rating_placements (ppo.rs:890-897); a game whose
+ * opponents all equal learner_player is skipped (main.rs:779-782).  *added = games appended, in
+ * record order.  ctx must be on the table's device (else BPPO_ERR_ARG).  The call is ordered after
+ * the context's stream and waits on the host only for its own kernels, to read *added. */
+bppo_status bppo_ratings_add_completions(bppo_ratings *r, bppo_ctx *ctx, int32_t learner_player,
+                                         const int32_t *slot_to_player, int32_t n_slots, int64_t *added);
+bppo_status bppo_ratings_num_games(const bppo_ratings *r, int64_t *n);
+/* compute_ratings (plackett_luce.rs:437-614): rating / uncertainty [num_players] on the Elo
+ * scale, gamma [num_players] (centred log-strengths before the anchor shift; may be NULL).
+ * Two fits of one table give identical bits, however the games were split over the add calls.
+ * BPPO_ERR_ARG before any launch: anchor outside [0, num_players), a stored player id
+ * >= num_players, num_players > 1024, backend 0 on a host-only table.
+ * The covariance inversion (invert_matrix, :361-425) runs on the host for both backends. */
+bppo_status bppo_ratings_fit(bppo_ratings *r, const bppo_pl_config *cfg, int32_t num_players, int32_t anchor,
+                             double *rating, double *uncertainty, double *gamma, bppo_pl_stats *stats);
+/* wall time (ms) of the last fit's phases, for scripts/bench_ratings.py: ms4 = {incidence list
+ * (backend 1: the expansion), MM iterations, Fisher information with its copy to the host, the
+ * host inversion + Elo conversion}; an early return leaves them as they were */
+bppo_status bppo_ratings_last_fit_phases(const bppo_ratings *r, double *ms4);
+size_t bppo_pl_config_size(void);
+size_t bppo_pl_stats_size(void);
+
 /* parity hooks: export / import a RolloutBuffer field.  names: "obs", "priv",
  * "actions" (i32), "rewards", "dones", "values", "log_probs", "advantages",
  * "returns", "players" (i32), "all_rewards", "masks", "last_v_pp", "perm" (u32,
