@@ -118,7 +118,7 @@ EXPORTS = (
     "bppo_set_explained_variance_mode", "bppo_set_minibatch_kernel", "bppo_set_rank",
     "bppo_debug_record_params",
     "bppo_evaluate", "bppo_eval_config_size", "bppo_eval_game_size", "bppo_debug_eval_sample",
-    "bppo_debug_eval_perms", "bppo_evaluate_pods", "bppo_evaluate_episodes",
+    "bppo_debug_eval_perms", "bppo_evaluate_pods", "bppo_evaluate_episodes", "bppo_debug_forward_groups",
     "bppo_opp_completion_size", "bppo_opponents_completions", "bppo_opponents_results",
     "bppo_ratings_create", "bppo_ratings_destroy", "bppo_ratings_last_error", "bppo_ratings_clear",
     "bppo_ratings_add_games", "bppo_ratings_add_completions", "bppo_ratings_num_games", "bppo_ratings_fit",
@@ -223,6 +223,7 @@ def lib():
                                          vp]),
         "bppo_debug_eval_sample": (i32, [i32, i32, i32, vp, vp, vp, u64, u64, u64, vp, vp]),
         "bppo_debug_eval_perms": (i32, [i32, vp]),
+        "bppo_debug_forward_groups": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "bppo_ratings_create": (i32, [C.c_int, vp, C.POINTER(vp)]),
         "bppo_ratings_destroy": (None, [vp]),
         "bppo_ratings_last_error": (C.c_char_p, [vp]),

@@ -279,6 +279,26 @@ def evaluate_pods_ctx(ctx, models, normalizers, pods, num_games, envs_per_pod, t
     return [(rec[k, :min(int(n[k]), int(num_games))], int(pos[k])) for k in range(n_pods)]
 
 
+def debug_forward_groups(ctx, mode, models, normalizers, gbase, xc):
+    """bppo_debug_forward_groups: the evaluation loop's actor forward of models[k] (None = the
+    random player, zero logits) on rows [gbase[k], gbase[k + 1]) of xc [rows][G + D].  mode 0: one
+    model after the other; mode 1: the grouped launches.  -> logits [rows][A]"""
+    K = len(models)
+    params, mean, m2, cnt, is_random = _pack_models(ctx, models, normalizers)
+    gb = np.ascontiguousarray(gbase, np.int32)
+    if gb.shape != (K + 1,):
+        raise ValueError("gbase has one entry per model and the end")
+    rows = int(gb[-1])
+    xc = np.ascontiguousarray(xc, np.float32)
+    if rows < 0 or xc.size != rows * (ctx.priv_dim + ctx.obs_dim):
+        raise ValueError("xc is [gbase[-1]][priv_dim + obs_dim]")
+    logits = np.zeros((rows, ctx.num_actions), np.float32)
+    L.check(L.lib().bppo_debug_forward_groups(ctx.h, int(mode), K, params.ctypes.data, mean.ctypes.data,
+                                              m2.ctypes.data, cnt.ctypes.data, is_random.ctypes.data, gb.ctypes.data,
+                                              xc.ctypes.data, logits.ctypes.data), ctx.h)
+    return logits
+
+
 def evaluate_pods(config, models, normalizers, pods, num_games, envs_per_pod, temp_schedule=None, seeds=None, seed=0,
                   device=0, max_steps=None):
     """Many matchups in one device loop (a tournament round): pod k plays num_games games

@@ -14,6 +14,22 @@ constexpr int GEMM_MAX_SPLITS = 1024;   // narrow conv weight gradients (Kin x C
 hipError_t gemm_fwd(hipStream_t st, int M, int N, int K, const float *X, int ldx, const float *W,
                     int ldw, const float *bias, int act, float *out0, int ld0, int n0, float *out1,
                     int ld1, int split = 0);
+// The actor forward of many models in one launch per layer (k_gemm_fwd_groups): model k owns
+// the rows [gbase[k + 1], gbase[k + 2]) of X and of out.
+struct FwdGroupTab {
+    static constexpr int MAX = 64;
+    const float *params[MAX];    // model k's parameters
+    const double *on[MAX];       // its obs normalizer block [mean D | m2 D | count]
+    uint8_t has_norm[MAX];       // whether the normalizer applies (count >= 2)
+    uint8_t skip[MAX];           // the random player: no forward, no tile
+};
+// One layer: out rows of group k = act(X rows W_k + b_k), W_k = params[k] + woff ([K][N]), b_k =
+// params[k] + boff.  gbase and tab are device memory; [span_r0, span_r0 + span_rows) bounds
+// the groups' rows (it sizes the grid, and the tanh pass of act 2 runs over it).  Per group
+// bit-identical to gemm_fwd on that group's rows.
+hipError_t gemm_fwd_groups(hipStream_t st, const int32_t *gbase, const FwdGroupTab *tab, int n_groups, int span_r0,
+                           int span_rows, int N, int K, const float *X, int ldx, size_t woff, size_t boff, int act,
+                           float *out, int ldo);
 // out = (dZ W^T) * act'(H) given the layer OUTPUT H (may be null: no factor):
 // act 2 tanh -> (1 - H^2), otherwise relu -> [H > 0].  dZ [M][K] (ldz), W [N][K] (ldw).
 // Each element is the k-ordered fmaf chain from 0 (the oracle's linear_bwd dx).  xa / xw

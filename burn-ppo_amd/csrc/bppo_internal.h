@@ -522,6 +522,10 @@ bppo_status wide_pack(bppo_ctx *c);
 bppo_status wide_forward(bppo_ctx *c, int rows, const float *xc, int ldxc, float *logits, float *values,
                          int split = 0);   // split: the update GEMMs on k_gemm_split (wide_minibatch)
 bppo_status wide_forward_actor(bppo_ctx *c, int rows, const float *xc, int ldxc, const float *params, float *logits);
+// the same for every model of an evaluation in one launch per layer (bppo_gemm.h FwdGroupTab)
+struct FwdGroupTab;
+bppo_status wide_forward_actor_groups(bppo_ctx *c, const int32_t *gbase, const FwdGroupTab *tab, int n_groups,
+                                      bool any_norm, int span_r0, int span_rows, float *xc, int ldxc, float *logits);
 // CNN trunk (cnn.hip): conv stack + flatten of `rows` obs rows -> d_cnn_f; backward
 // of the conv stack from dF (dL/d features, [rows][fdim]) into the gradient
 bppo_status cnn_alloc(bppo_ctx *c);

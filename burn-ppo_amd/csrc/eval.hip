@@ -17,11 +17,14 @@
 //                    slots ascending, within a slot the non-frozen envs in ascending index
 //                    (eval.rs:1685-1769); the (model, pod) row counts
 //   k_eval_scan      the counts scanned model-major, pod-minor: each env's row, the header
-//   one host read    {unfinished pods, error flags, group bases}: sizes the per-model
-//                    GEMMs and ends the loop (eval.rs:1670-1674)
-//   per model        rows sorted (k_opp_sort_rows), its obs normalizer
-//                    (eval.rs:1727-1734), wide_forward_actor, logits selected back
-//                    (k_opp_select); a random model's rows see zero logits (eval.rs:1749-1752)
+//   one host read    {unfinished pods, error flags, group bases}: bounds the forward's
+//                    grids and ends the loop (eval.rs:1670-1674)
+//   forward          rows sorted model-major (k_opp_sort_rows); all models at once: one
+//                    obs normalizer launch (eval.rs:1727-1734) and one GEMM launch per layer
+//                    over every model's row range, read from the header on the device
+//                    (wide_forward_actor_groups); logits selected back
+//                    (k_opp_select); a random model's rows see zero logits (eval.rs:1749-1752).
+//                    Nets with conv layers: one model after the other (wide_forward_actor)
 //   k_eval_sample    sample_with_temperature per row at the pod's word position + draw index
 //   env step         k_wide_step with the frozen mask, the outcome sink and per-env seeds
 //   k_eval_finish    one block per pod: games recorded in env order up to the cap, seat ->
@@ -40,6 +43,7 @@
 #include "bppo_envs.h"
 #include "bppo_wide.h"
 #include "bppo_eval.h"
+#include "bppo_gemm.h"
 #include "bppo_scan.h"
 
 namespace bppo {
@@ -446,6 +450,69 @@ extern "C" bppo_status bppo_debug_eval_sample(int32_t device, int32_t A, int32_t
     return (err & EV_ERR_ZERO_SUM) ? BPPO_ERR_NONFINITE : BPPO_OK;
 }
 
+// The models of one evaluation on the device: parameters [K][n_params], normalizer blocks
+// [K][mean D | m2 D | count], and the table the grouped forward reads them through.  The
+// uploads are ordered on the context's stream and read this struct's host arrays: it
+// outlives the stream's next drain.
+struct EvalModels {
+    float *d_params = nullptr;
+    double *d_on = nullptr;
+    FwdGroupTab *d_tab = nullptr;
+    FwdGroupTab tab{};
+    std::vector<double> on;
+    bool any_norm = false;
+};
+static bppo_status upload_models(bppo_ctx *c, EvalBuffers &buf, EvalModels &m, int K, const float *params,
+                                 const double *norm_mean, const double *norm_m2, const double *norm_count,
+                                 uint64_t random_models) {
+    const int D = c->D;
+    const size_t np = c->net.n_params, nb = (size_t)(2 * D + 1);
+    BPPO_HIP(c, buf.alloc(&m.d_params, np * K));
+    BPPO_HIP(c, buf.alloc(&m.d_on, nb * K));
+    BPPO_HIP(c, buf.alloc(&m.d_tab, 1));
+    m.on.assign(nb * K, 0.0);
+    for (int k = 0; k < K; k++) {
+        m.tab.params[k] = m.d_params + (size_t)k * np;
+        m.tab.on[k] = m.d_on + (size_t)k * nb;
+        m.tab.skip[k] = (uint8_t)((random_models >> k) & 1ull);
+        if (m.tab.skip[k]) continue;
+        BPPO_HIP(c, hipMemcpyAsync(m.d_params + (size_t)k * np, params + (size_t)k * np, sizeof(float) * np,
+                                   hipMemcpyHostToDevice, c->stream));
+        if (!norm_count || norm_count[k] < 2.0 || !norm_mean || !norm_m2) continue;
+        m.tab.has_norm[k] = 1;
+        m.any_norm = true;
+        std::memcpy(&m.on[(size_t)k * nb], norm_mean + (size_t)k * D, sizeof(double) * D);
+        std::memcpy(&m.on[(size_t)k * nb + D], norm_m2 + (size_t)k * D, sizeof(double) * D);
+        m.on[(size_t)k * nb + 2 * D] = norm_count[k];
+    }
+    BPPO_HIP(c, hipMemcpyAsync(m.d_on, m.on.data(), sizeof(double) * m.on.size(), hipMemcpyHostToDevice, c->stream));
+    BPPO_HIP(c, hipMemcpyAsync(m.d_tab, &m.tab, sizeof(FwdGroupTab), hipMemcpyHostToDevice, c->stream));
+    return BPPO_OK;
+}
+
+// The forward one model after the other, sized by the host's copy of the group bases gb
+// [K + 2]: the path of nets with conv layers (their im2col scratch holds one model's rows),
+// and mode 0 of bppo_debug_forward_groups.
+static bppo_status forward_models_loop(bppo_ctx *c, int K, const EvalModels &m, const int32_t *gb, float *d_oxc,
+                                       float *d_ologits) {
+    const int A = c->A, L = c->L;
+    for (int k = 0; k < K; k++) {
+        const int r0 = gb[k + 1], rows = gb[k + 2] - gb[k + 1];
+        if (rows <= 0 || m.tab.skip[k]) continue;
+        float *x = d_oxc + (size_t)r0 * L;
+        if (m.tab.has_norm[k]) TRY(launch_obs_norm_rows_on(c, rows, x + c->G, L, nullptr, m.tab.on[k]));
+        TRY(wide_forward_actor(c, rows, x, L, m.tab.params[k], d_ologits + (size_t)r0 * A));
+    }
+    return BPPO_OK;
+}
+// All models at once from the device's group bases d_gbase (nets without conv layers); the
+// host's copy gives only the span of rows.
+static bppo_status forward_models(bppo_ctx *c, int K, const EvalModels &m, const int32_t *gb, const int32_t *d_gbase,
+                                  float *d_oxc, float *d_ologits) {
+    if (c->net.n_conv) return forward_models_loop(c, K, m, gb, d_oxc, d_ologits);
+    return wide_forward_actor_groups(c, d_gbase, m.d_tab, K, m.any_norm, gb[1], gb[K + 1] - gb[1], d_oxc, c->L, d_ologits);
+}
+
 static uint64_t random_mask(const int32_t *is_random, int K) {
     uint64_t m = 0;
     for (int k = 0; k < K; k++)
@@ -495,8 +562,8 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
     EvalBuffers buf;
     EvalState s{};
     int32_t *d_perm_tab = nullptr, *d_seat_model = nullptr, *d_slot_model = nullptr;
-    float *d_params = nullptr, *d_oxc = nullptr, *d_ologits = nullptr;
-    double *d_on = nullptr;
+    float *d_oxc = nullptr, *d_ologits = nullptr;
+    EvalModels mod;
     EvalOutcome *d_sink = nullptr;
     bppo_eval_game *d_games = nullptr;
     Key8 *d_keys = nullptr;
@@ -523,8 +590,6 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
     BPPO_HIP(c, buf.alloc(&s.ndraw, (size_t)n_pods));
     BPPO_HIP(c, buf.alloc(&s.rngpos, (size_t)n_pods));
     BPPO_HIP(c, buf.alloc(&s.hdr, 1));
-    BPPO_HIP(c, buf.alloc(&d_params, np * K));
-    BPPO_HIP(c, buf.alloc(&d_on, (size_t)(2 * D + 1) * K));
     BPPO_HIP(c, buf.alloc(&d_oxc, (size_t)N * L));
     BPPO_HIP(c, buf.alloc(&d_ologits, (size_t)N * A));
     BPPO_HIP(c, buf.alloc(&d_sink, (size_t)N));
@@ -536,19 +601,7 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
     s.err = c->d_err;
 
     // models: uploads ordered on the context's stream, drained before the host arrays may go
-    std::vector<int> has_norm((size_t)K, 0);
-    std::vector<double> on((size_t)(2 * D + 1) * K, 0.0);
-    for (int k = 0; k < K; k++) {
-        if ((random_models >> k) & 1ull) continue;
-        BPPO_HIP(c, hipMemcpyAsync(d_params + (size_t)k * np, params + (size_t)k * np, sizeof(float) * np,
-                                   hipMemcpyHostToDevice, c->stream));
-        if (!norm_count || norm_count[k] < 2.0 || !norm_mean || !norm_m2) continue;
-        has_norm[k] = 1;
-        std::memcpy(&on[(size_t)k * (2 * D + 1)], norm_mean + (size_t)k * D, sizeof(double) * D);
-        std::memcpy(&on[(size_t)k * (2 * D + 1) + D], norm_m2 + (size_t)k * D, sizeof(double) * D);
-        on[(size_t)k * (2 * D + 1) + 2 * D] = norm_count[k];
-    }
-    BPPO_HIP(c, hipMemcpyAsync(d_on, on.data(), sizeof(double) * on.size(), hipMemcpyHostToDevice, c->stream));
+    TRY(upload_models(c, buf, mod, K, params, norm_mean, norm_m2, norm_count, random_models));
     BPPO_HIP(c, hipMemcpyAsync(d_perm_tab, perms.data(), sizeof(int32_t) * perms.size(), hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_seat_model, pod_seat_model, sizeof(int32_t) * (size_t)n_pods * P, hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_slot_model, slot_model.data(), sizeof(int32_t) * slot_model.size(), hipMemcpyHostToDevice, c->stream));
@@ -589,13 +642,7 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
         for (int k = 0; k < K; k++) any_fwd = any_fwd || (!((random_models >> k) & 1ull) && gb[k + 2] > gb[k + 1]);
         if (any_fwd) {
             TRY(opp_sort_rows(c, s.group, s.gpos, c->d_bxc, d_oxc));
-            for (int k = 0; k < K; k++) {
-                const int r0 = gb[k + 1], rows = gb[k + 2] - gb[k + 1];
-                if (rows <= 0 || ((random_models >> k) & 1ull)) continue;
-                float *x = d_oxc + (size_t)r0 * L;
-                if (has_norm[k]) TRY(launch_obs_norm_rows_on(c, rows, x + c->G, L, nullptr, d_on + (size_t)k * (2 * D + 1)));
-                TRY(wide_forward_actor(c, rows, x, L, d_params + (size_t)k * np, d_ologits + (size_t)r0 * A));
-            }
+            TRY(forward_models(c, K, mod, gb, s.hdr->gbase, d_oxc, d_ologits));
             TRY(opp_select(c, s.group, s.gpos, d_ologits, c->d_logits));
         }
         EvalSampleArgs g;
@@ -707,4 +754,53 @@ extern "C" bppo_status bppo_evaluate_pods(bppo_ctx *c, const bppo_eval_config *c
         pod_slots(pod_seat_model + (size_t)k * P, P, false, &slot_model[(size_t)k * P]);
     return evaluate_run(c, "evaluate_pods", cfg, K, params, norm_mean, norm_m2, norm_count, random_models, n_pods, E,
                         pod_seeds, pod_seat_model, slot_model, games, cap_per_pod, n_games, rng_word_pos);
+}
+
+// Parity hook of the grouped forward: model k's rows are [gbase[k], gbase[k + 1]) of xc
+// [gbase[n_models]][L] (rows before gbase[0] belong to nobody, as the frozen group's); logits
+// [gbase[n_models]][A], a random model's rows and those before gbase[0] zero.  mode 0: one
+// model after the other (launch_obs_norm_rows_on + wide_forward_actor); mode 1: the grouped
+// launches.  The context gives the net shape, the stream and the hidden buffers d_hbuf, which
+// are overwritten: a rollout not yet bootstrapped is dropped, as evaluate_run drops it; the
+// context's parameters are not read.
+extern "C" bppo_status bppo_debug_forward_groups(bppo_ctx *c, int32_t mode, int32_t n_models, const float *params,
+                                                 const double *norm_mean, const double *norm_m2,
+                                                 const double *norm_count, const int32_t *is_random,
+                                                 const int32_t *gbase, const float *xc, float *logits) {
+    if (!c) return BPPO_ERR_ARG;
+    if (!c->wide || c->cfg.env_kind == BPPO_ENV_CARTPOLE) { c->err = "debug_forward_groups: multi-player envs only"; return BPPO_ERR_UNSUPPORTED; }
+    if (mode != 0 && mode != 1) { c->err = "debug_forward_groups: mode 0 or 1"; return BPPO_ERR_ARG; }
+    if (mode == 1 && c->net.n_conv) { c->err = "debug_forward_groups: nets with conv layers have no grouped forward"; return BPPO_ERR_UNSUPPORTED; }
+    if (!gbase || !xc || !logits) { c->err = "debug_forward_groups: NULL argument"; return BPPO_ERR_ARG; }
+    if (n_models < 1 || n_models > EV_MAX_MODELS) { c->err = "debug_forward_groups: 1..64 models"; return BPPO_ERR_ARG; }
+    const int K = n_models, A = c->A, L = c->L;
+    std::vector<int32_t> gb((size_t)K + 2, 0);
+    for (int k = 0; k <= K; k++) {
+        if (gbase[k] < gb[k]) { c->err = "debug_forward_groups: gbase must start at >= 0 and not decrease"; return BPPO_ERR_ARG; }
+        gb[k + 1] = gbase[k];
+    }
+    const int rows = gb[K + 1];
+    if (rows > c->rows_max) { c->err = "debug_forward_groups: more rows than the context's buffers hold"; return BPPO_ERR_ARG; }
+    const uint64_t random_models = random_mask(is_random, K);
+    const uint64_t all_models = K == 64 ? ~0ull : (1ull << K) - 1ull;
+    if (random_models != all_models && !params) { c->err = "debug_forward_groups: model parameters required"; return BPPO_ERR_ARG; }
+    if (rows == 0) return BPPO_OK;
+    drop_prefetch(c);
+    if (!c->gae_done) c->collected = 0;       // the hidden buffers are the rollout's
+    EvalBuffers buf;
+    EvalModels mod;
+    int32_t *d_gb = nullptr;
+    float *d_x = nullptr, *d_l = nullptr;
+    BPPO_HIP(c, buf.alloc(&d_gb, gb.size()));
+    BPPO_HIP(c, buf.alloc(&d_x, (size_t)rows * L));
+    BPPO_HIP(c, buf.alloc(&d_l, (size_t)rows * A));
+    TRY(upload_models(c, buf, mod, K, params, norm_mean, norm_m2, norm_count, random_models));
+    BPPO_HIP(c, hipMemcpyAsync(d_gb, gb.data(), sizeof(int32_t) * gb.size(), hipMemcpyHostToDevice, c->stream));
+    BPPO_HIP(c, hipMemcpyAsync(d_x, xc, sizeof(float) * (size_t)rows * L, hipMemcpyHostToDevice, c->stream));
+    BPPO_HIP(c, hipMemsetAsync(d_l, 0, sizeof(float) * (size_t)rows * A, c->stream));
+    if (mode == 0) TRY(forward_models_loop(c, K, mod, gb.data(), d_x, d_l));
+    else TRY(wide_forward_actor_groups(c, d_gb, mod.d_tab, K, mod.any_norm, gb[1], gb[K + 1] - gb[1], d_x, L, d_l));
+    BPPO_HIP(c, hipMemcpyAsync(logits, d_l, sizeof(float) * (size_t)rows * A, hipMemcpyDeviceToHost, c->stream));
+    BPPO_HIP(c, hipStreamSynchronize(c->stream));
+    return BPPO_OK;
 }

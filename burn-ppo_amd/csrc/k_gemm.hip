@@ -388,6 +388,113 @@ __global__ void __launch_bounds__(256, 2) k_gemm(GemmArgs g) {
     }
 }
 
+// ---- grouped forward: the actor layers of all the models of an evaluation, one launch ----
+// Group k is the rows [gbase[k + 1], gbase[k + 2]) of one row buffer (EvalHdr::gbase, device
+// memory, written by k_eval_scan earlier on the stream) with model k's weights and bias
+// (FwdGroupTab::params[k] + the layer's offsets).  blockIdx.y counts the row tiles of the
+// groups that have one, in group order; the grid is an upper bound and a block past the last
+// tile returns before it touches shared memory.  From there on it is k_gemm<GEMM_FWD>'s loop
+// on the rows [m0, mend) -- the same loaders, the same k-ordered MFMA chain restarted every
+// KC, the same epilogue -- so a row's result is gemm_fwd's on that group alone, bit for bit
+// (tests/test_gpu_tournament.py).  The loop is restated here, not shared: k_gemm's
+// instantiations keep their registers and code as they are.
+struct GroupFwdArgs {
+    const int32_t *gbase;        // device: [n_groups + 2]
+    const FwdGroupTab *tab;      // device
+    int n_groups;
+    const float *X; int ldx;     // row buffer, the layer's input columns
+    size_t woff, boff;           // the layer's W [K][N] and bias [N] inside a model's parameters
+    int N, K, act;               // act: 1 relu, 0 none
+    float *out; int ldo;
+};
+template <int BM, int BN, int WM, int WN>
+__global__ void __launch_bounds__(256, 2) k_gemm_fwd_groups(GroupFwdArgs a) {
+    using S = GemmShape<BM, BN, WM, WN>;
+    int t = blockIdx.y, grp = -1, m0 = 0, mend = 0;
+    for (int k = 0; k < a.n_groups; k++) {
+        if (a.tab->skip[k]) continue;                       // the random player: no forward
+        const int r0 = a.gbase[k + 1], r1 = a.gbase[k + 2];
+        const int tiles = r1 > r0 ? (r1 - r0 + BM - 1) / BM : 0;
+        if (t < tiles) { grp = k; m0 = r0 + t * BM; mend = r1; break; }
+        t -= tiles;
+    }
+    if (grp < 0) return;                                    // uniform over the block
+    GemmArgs g{};
+    g.A = a.X; g.lda = a.ldx; g.B = a.tab->params[grp] + a.woff; g.ldb = a.N; g.M = mend; g.N = a.N; g.K = a.K;
+    g.bias = a.tab->params[grp] + a.boff; g.act = a.act;
+    g.out0 = a.out; g.ld0 = a.ldo; g.n0 = a.N; g.out1 = nullptr; g.ld1 = 0;
+    __shared__ float sA[2][GBK * S::APAD];
+    __shared__ float sB[2][GBK * S::BPAD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave / WN, wn = wave % WN;
+    const int n0 = blockIdx.x * BN, kend = g.K;
+    TileLoader<BM, true> la;
+    TileLoader<BN, false> lb;
+    f32x16 acc[S::TM][S::TN], tot[S::TM][S::TN];
+#pragma unroll
+    for (int i = 0; i < S::TM; i++)
+#pragma unroll
+        for (int j = 0; j < S::TN; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) { acc[i][j][r] = 0.0f; tot[i][j][r] = 0.0f; }
+    la.load(g.A, g.lda, m0, g.M, 0, kend, tid);
+    lb.load(g.B, g.ldb, n0, g.N, 0, kend, tid);
+    la.store(sA[0], tid);
+    lb.store(sB[0], tid);
+    __syncthreads();
+    int buf = 0;
+    for (int k0 = 0; k0 < kend; k0 += GBK) {
+        const bool more = k0 + GBK < kend;
+        if (more) {
+            la.load(g.A, g.lda, m0, g.M, k0 + GBK, kend, tid);
+            lb.load(g.B, g.ldb, n0, g.N, k0 + GBK, kend, tid);
+        }
+        const float *sa = sA[buf], *sb = sB[buf];
+        const int h = lane >> 5, r = lane & 31;
+#pragma unroll
+        for (int kk = 0; kk < GBK; kk += 2) {
+            float af[S::TM], bf[S::TN];
+#pragma unroll
+            for (int i = 0; i < S::TM; i++) af[i] = sa[(kk + h) * S::APAD + (wm * S::TM + i) * 32 + r];
+#pragma unroll
+            for (int j = 0; j < S::TN; j++) bf[j] = sb[(kk + h) * S::BPAD + (wn * S::TN + j) * 32 + r];
+#pragma unroll
+            for (int i = 0; i < S::TM; i++)
+#pragma unroll
+                for (int j = 0; j < S::TN; j++)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
+        }
+        // the KC block boundary, as in k_gemm<GEMM_FWD>
+        if (((k0 + GBK) % KC) == 0 && more) {
+#pragma unroll
+            for (int i = 0; i < S::TM; i++)
+#pragma unroll
+                for (int j = 0; j < S::TN; j++)
+#pragma unroll
+                    for (int q = 0; q < 16; q++) {
+                        tot[i][j][q] = (k0 + GBK == KC) ? acc[i][j][q] : __fadd_rn(tot[i][j][q], acc[i][j][q]);
+                        acc[i][j][q] = 0.0f;
+                    }
+        }
+        if (more) {
+            __syncthreads();
+            la.store(sA[buf ^ 1], tid);
+            lb.store(sB[buf ^ 1], tid);
+            __syncthreads();
+            buf ^= 1;
+        }
+    }
+    if (g.K > KC) {
+#pragma unroll
+        for (int i = 0; i < S::TM; i++)
+#pragma unroll
+            for (int j = 0; j < S::TN; j++)
+#pragma unroll
+                for (int q = 0; q < 16; q++) acc[i][j][q] = __fadd_rn(tot[i][j][q], acc[i][j][q]);
+    }
+    gemm_epilogue<GEMM_FWD, S::TM, S::TN>(g, acc, Tile{0, 0, 0}, m0 + wm * S::TM * 32, n0 + wn * S::TN * 32, lane);
+}
+
 // ---- split-bf16 contraction (every update minibatch after the first) -----------------
 // The forward, input-gradient and weight-gradient GEMMs of the update's later minibatches
 // need f32 ACCURACY, not the reference's rounding: their parameters already differ from
@@ -991,6 +1098,31 @@ static hipError_t wgrad(hipStream_t st, const ConvA &cv, int Kin, int N, int row
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+template <int BM, int BN, int WM, int WN>
+static hipError_t launch_groups(const GroupFwdArgs &a, int rows_bound, hipStream_t st) {
+    // at most ceil(rows / BM) whole tiles plus one partial tile per group (rows counts the
+    // random models' rows too, which get no tile: an upper bound, a few blocks too many)
+    dim3 grid((a.N + BN - 1) / BN, (rows_bound + BM - 1) / BM + a.n_groups, 1);
+    hipLaunchKernelGGL((k_gemm_fwd_groups<BM, BN, WM, WN>), grid, dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t gemm_fwd_groups(hipStream_t st, const int32_t *gbase, const FwdGroupTab *tab, int n_groups, int span_r0,
+                           int span_rows, int N, int K, const float *X, int ldx, size_t woff, size_t boff, int act,
+                           float *out, int ldo) {
+    if (span_rows <= 0 || N <= 0 || n_groups <= 0) return hipSuccess;
+    GroupFwdArgs a{};
+    a.gbase = gbase; a.tab = tab; a.n_groups = n_groups; a.X = X; a.ldx = ldx; a.woff = woff; a.boff = boff;
+    a.N = N; a.K = K; a.act = act == 1 ? 1 : 0; a.out = out; a.ldo = ldo;
+    hipError_t e;
+    if (N <= 32) e = launch_groups<128, 32, 4, 1>(a, span_rows, st);          // launch_by_width's shapes
+    else if (N <= 64) e = launch_groups<128, 64, 4, 1>(a, span_rows, st);
+    else e = launch_groups<128, 128, 2, 2>(a, span_rows, st);
+    if (e != hipSuccess || act != 2) return e;
+    // over the whole span: the rows of a random model's group inside it were written by no
+    // tile and hold whatever the buffer held; tanh of that faults nothing and nobody reads it
+    return tanh_inplace(st, out + (size_t)span_r0 * ldo, span_rows, N, ldo);
 }
 
 }  // namespace bppo

@@ -626,6 +626,22 @@ bppo_status bppo_debug_eval_perms(int32_t n, int32_t *out);
  * mode 2: out[M][N] = A[K][M]^T B[K][N] (weight gradient), out2[N] = column sums of B */
 bppo_status bppo_debug_gemm(int32_t mode, int32_t M, int32_t N, int32_t K, const float *A, const float *B,
                             const float *bias_or_H, int32_t act, float *out, float *out2);
+/* Parity hook of the evaluation loop's forward (host buffers): the actor logits of n_models
+ * models' row groups.  Model k owns rows [gbase[k], gbase[k + 1]) of xc [gbase[n_models]][G + D]
+ * ([priv | obs] rows, raw: a model's obs normalizer is applied as the loop applies it) and of
+ * logits [gbase[n_models]][A]; gbase has n_models + 1 entries, starts at >= 0 and does not
+ * decrease.  params [n_models][n_params], norm_* and is_random as bppo_evaluate_pods takes them;
+ * a random model's rows get zero logits.  mode 0: one model after the other (the launches of
+ * bppo_forward); mode 1: the grouped launches, one per layer over all groups, which the loop
+ * uses for every net without conv layers.  The context gives the net shape, the stream and
+ * its hidden activation buffers, which are overwritten: as bppo_evaluate does, the call drops
+ * a rollout that has not been bootstrapped yet (bppo_compute_gae) and a prefetched one.  The
+ * context's parameters, envs and RNG are not touched.  At most as many rows as its buffers
+ * hold (max(num_envs, minibatch size)). */
+bppo_status bppo_debug_forward_groups(bppo_ctx *ctx, int32_t mode, int32_t n_models, const float *params,
+                                      const double *norm_mean, const double *norm_m2, const double *norm_count,
+                                      const int32_t *is_random, const int32_t *gbase, const float *xc,
+                                      float *logits);
 
 #ifdef __cplusplus
 }
