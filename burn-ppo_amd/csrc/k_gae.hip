@@ -403,18 +403,26 @@ __global__ void k_rn_returns(int T, int N, double gamma, const float *__restrict
 // that player when the step ends the episode.  X in (t, e) order as above.
 // valid (opponent pool, nullable): only learner turns enter the variance stats
 // (ppo.rs:982-989); other rows carry a NaN in X, which the scan skips
-__global__ void k_rn_returns_mp(int T, int N, int P, double gamma, const float *rew_raw, const float *done,
+// P is a template parameter (1..BPPO_MAX_PLAYERS, as k_gae_mp<P>): one register per player,
+// selected and written back with unrolled compares, so a 5- or 6-seat Skull table keeps
+// every seat's return
+template <int P>
+__global__ void k_rn_returns_mp(int T, int N, double gamma, const float *rew_raw, const float *done,
                                 const int32_t *players, const float *valid, double *returns_state, double *X) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
-    double R0 = returns_state[(size_t)e * P], R1 = P > 1 ? returns_state[(size_t)e * P + 1] : 0.0;
-    double R2 = P > 2 ? returns_state[(size_t)e * P + 2] : 0.0, R3 = P > 3 ? returns_state[(size_t)e * P + 3] : 0.0;
+    double R[P];
+#pragma unroll
+    for (int q = 0; q < P; q++) R[q] = returns_state[(size_t)e * P + q];
     auto step = [&](size_t i, int p, float r, float d, bool ok) {
-        double x = p == 0 ? R0 : p == 1 ? R1 : p == 2 ? R2 : R3;
+        double x = R[0];
+#pragma unroll
+        for (int q = 1; q < P; q++) x = p == q ? R[q] : x;
         x = x * gamma + (double)r;
         X[i] = ok ? x : __longlong_as_double(0x7ff8000000000000ll);
         if (d != 0.0f) x = 0.0;
-        R0 = p == 0 ? x : R0; R1 = p == 1 ? x : R1; R2 = p == 2 ? x : R2; R3 = p == 3 ? x : R3;
+#pragma unroll
+        for (int q = 0; q < P; q++) R[q] = p == q ? x : R[q];
     };
     const bool has_valid = valid != nullptr;
     const float *vsrc = has_valid ? valid : done;  // read unconditionally (a guarded load was a branch + wait)
@@ -437,10 +445,8 @@ __global__ void k_rn_returns_mp(int T, int N, int P, double gamma, const float *
         const size_t i = (size_t)t0 * N + e;
         step(i, players[i], rew_raw[i], done[i], !valid || valid[i] > 0.5f);
     }
-    returns_state[(size_t)e * P] = R0;
-    if (P > 1) returns_state[(size_t)e * P + 1] = R1;
-    if (P > 2) returns_state[(size_t)e * P + 2] = R2;
-    if (P > 3) returns_state[(size_t)e * P + 3] = R3;
+#pragma unroll
+    for (int q = 0; q < P; q++) returns_state[(size_t)e * P + q] = R[q];
 }
 
 // ppo.rs:412-428: the acting player's entry of all_rewards is the normalized
@@ -558,27 +564,107 @@ __global__ void __launch_bounds__(RN_BLOCK) k_rn_apply(size_t n, const double *X
         if (b0 + k < n) rew[b0 + k] = rs[(k / RN_IPT) * RN_PAD + (k % RN_IPT)];
 }
 
-bppo_status launch_return_norm(bppo_ctx *c) {
-    const size_t n = (size_t)c->T * c->N;
+// the launches on plain device pointers: players == nullptr runs the single-player kernel
+// (P = 1), otherwise the per-player one and, with all_r, the scatter of the acting reward.
+// agg holds ceil(T N / RN_SEG) + 1 Welford states, X T N doubles
+bppo_status launch_return_norm_raw(int T, int N, int P, double gamma, float clip, const float *rew_raw,
+                                   const float *done, const int32_t *players, const float *valid,
+                                   double *returns_state, double *stats, double *X, Welford *agg, float *rew,
+                                   float *all_r, hipStream_t s, hipError_t *herr) {
+    if (T <= 0 || N <= 0) return BPPO_OK;
+    const size_t n = (size_t)T * N;
     const int nb = (int)((n + RN_SEG - 1) / RN_SEG);
-    if (c->wide)
-        hipLaunchKernelGGL(k_rn_returns_mp, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, c->T, c->N, c->P,
-                           c->cfg.gamma, c->d_rew_raw, c->d_done, c->d_players, c->n_opp ? c->d_valid : nullptr,
-                           c->d_rn_returns, c->d_X);
-    else
-        hipLaunchKernelGGL(k_rn_returns, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, c->T, c->N,
-                           c->cfg.gamma, c->d_rew_raw, c->d_done, c->d_rn_returns, c->d_X);
-    hipLaunchKernelGGL(k_rn_block_agg, dim3(nb), dim3(RN_BLOCK), 0, c->stream, n, c->d_X,
-                       c->d_scan_agg);
-    hipLaunchKernelGGL(k_rn_agg_scan, dim3(1), dim3(1024), 0, c->stream, nb, c->d_scan_agg,
-                       c->d_rn_stats);
-    hipLaunchKernelGGL(k_rn_apply, dim3(nb), dim3(RN_BLOCK), 0, c->stream, n, c->d_X, c->d_rew_raw,
-                       c->d_scan_agg, (float)c->cfg.return_clip, c->d_rew);
-    if (c->wide)
+    if (players) {
+        const dim3 g((N + 255) / 256), b(256);
+#define RNMP(P_) hipLaunchKernelGGL(k_rn_returns_mp<P_>, g, b, 0, s, T, N, gamma, rew_raw, done, players, valid, returns_state, X)
+        switch (P) {
+        case 1: RNMP(1); break;
+        case 2: RNMP(2); break;
+        case 3: RNMP(3); break;
+        case 4: RNMP(4); break;
+        case 5: RNMP(5); break;
+        case 6: RNMP(6); break;
+        default: return BPPO_ERR_ARG;
+        }
+#undef RNMP
+    } else
+        hipLaunchKernelGGL(k_rn_returns, dim3((N + 255) / 256), dim3(256), 0, s, T, N, gamma, rew_raw, done,
+                           returns_state, X);
+    hipLaunchKernelGGL(k_rn_block_agg, dim3(nb), dim3(RN_BLOCK), 0, s, n, X, agg);
+    hipLaunchKernelGGL(k_rn_agg_scan, dim3(1), dim3(1024), 0, s, nb, agg, stats);
+    hipLaunchKernelGGL(k_rn_apply, dim3(nb), dim3(RN_BLOCK), 0, s, n, X, rew_raw, agg, clip, rew);
+    if (players && all_r)
         hipLaunchKernelGGL(k_rn_scatter_acting, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0,
-                           c->stream, n, c->P, c->d_players, c->d_rew, c->d_allr);
-    TRY(launch_check(c, __func__));
-    return BPPO_OK;
+                           s, n, P, players, rew, all_r);
+    const hipError_t e = hipGetLastError();
+    if (herr) *herr = e;
+    return e == hipSuccess ? BPPO_OK : BPPO_ERR_HIP;
+}
+
+bppo_status launch_return_norm(bppo_ctx *c) {
+    hipError_t e = hipSuccess;
+    const bppo_status st =
+        launch_return_norm_raw(c->T, c->N, c->P, c->cfg.gamma, (float)c->cfg.return_clip, c->d_rew_raw, c->d_done,
+                               c->wide ? c->d_players : nullptr, c->wide && c->n_opp ? c->d_valid : nullptr,
+                               c->d_rn_returns, c->d_rn_stats, c->d_X, c->d_scan_agg, c->d_rew,
+                               c->wide ? c->d_allr : nullptr, c->stream, &e);
+    if (st == BPPO_ERR_HIP) return hip_fail(c, e, __func__);
+    return st;
 }
 
 }  // namespace bppo
+
+// ------------------------------------------------------------ parity hook ---
+// bppo_debug_return_norm: host buffers in/out, the launches of launch_return_norm on
+// temporaries of its own (X, and the block aggregates sized as ctx_init sizes them)
+extern "C" bppo_status bppo_debug_return_norm(int32_t T, int32_t N, int32_t P, double gamma, float clip,
+                                              const float *rew_raw, const float *done, const int32_t *players,
+                                              const float *valid, double *returns_state, double *stats3, float *rew,
+                                              float *all_rewards) {
+    using namespace bppo;
+    if (T < 1 || N < 1 || P < 1 || P > BPPO_MAX_PLAYERS || !rew_raw || !done || !returns_state || !stats3 || !rew)
+        return BPPO_ERR_ARG;
+    // the single-player kernel: one return per env, every row counts, no all_rewards
+    if (!players && (P != 1 || valid || all_rewards)) return BPPO_ERR_ARG;
+    const size_t n = (size_t)T * N, nP = (size_t)N * P;
+    float *d_raw = nullptr, *d_done = nullptr, *d_valid = nullptr, *d_rew = nullptr, *d_allr = nullptr;
+    int32_t *d_pl = nullptr;
+    double *d_ret = nullptr, *d_stats = nullptr, *d_X = nullptr;
+    Welford *d_agg = nullptr;
+    bppo_status s = BPPO_ERR_HIP;
+    do {
+        if (hipMalloc((void **)&d_raw, n * 4) != hipSuccess || hipMalloc((void **)&d_done, n * 4) != hipSuccess) break;
+        if (hipMalloc((void **)&d_rew, n * 4) != hipSuccess || hipMalloc((void **)&d_X, n * 8) != hipSuccess) break;
+        if (hipMalloc((void **)&d_ret, nP * 8) != hipSuccess || hipMalloc((void **)&d_stats, 4 * 8) != hipSuccess) break;
+        if (hipMalloc((void **)&d_agg, ((n + 4095) / 4096 + 1) * sizeof(Welford)) != hipSuccess) break;
+        if (hipMemcpy(d_raw, rew_raw, n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(d_done, done, n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(d_ret, returns_state, nP * 8, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(d_stats, stats3, 3 * 8, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (players) {
+            if (hipMalloc((void **)&d_pl, n * 4) != hipSuccess) break;
+            if (hipMemcpy(d_pl, players, n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        }
+        if (valid) {
+            if (hipMalloc((void **)&d_valid, n * 4) != hipSuccess) break;
+            if (hipMemcpy(d_valid, valid, n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        }
+        if (all_rewards) {
+            if (hipMalloc((void **)&d_allr, n * P * 4) != hipSuccess) break;
+            if (hipMemcpy(d_allr, all_rewards, n * P * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        }
+        s = launch_return_norm_raw(T, N, P, gamma, clip, d_raw, d_done, d_pl, d_valid, d_ret, d_stats, d_X, d_agg,
+                                   d_rew, d_allr, nullptr, nullptr);
+        if (s != BPPO_OK) break;
+        s = BPPO_ERR_HIP;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        if (hipMemcpy(rew, d_rew, n * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (hipMemcpy(returns_state, d_ret, nP * 8, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (hipMemcpy(stats3, d_stats, 3 * 8, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (all_rewards && hipMemcpy(all_rewards, d_allr, n * P * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
+        s = BPPO_OK;
+    } while (0);
+    (void)hipFree(d_raw); (void)hipFree(d_done); (void)hipFree(d_valid); (void)hipFree(d_rew); (void)hipFree(d_allr);
+    (void)hipFree(d_pl); (void)hipFree(d_ret); (void)hipFree(d_stats); (void)hipFree(d_X); (void)hipFree(d_agg);
+    return s;
+}

@@ -626,6 +626,21 @@ bppo_status bppo_debug_eval_perms(int32_t n, int32_t *out);
  * mode 2: out[M][N] = A[K][M]^T B[K][N] (weight gradient), out2[N] = column sums of B */
 bppo_status bppo_debug_gemm(int32_t mode, int32_t M, int32_t N, int32_t K, const float *A, const float *B,
                             const float *bias_or_H, int32_t act, float *out, float *out2);
+/* ReturnNormalizer parity hook (host buffers, no context): the kernels and launch order of a
+ * rollout's return normalization (normalization.rs:156-197, ppo.rs:388-428) over T steps of N
+ * envs.  For t ascending, e ascending: the acting player's rolling return R = R gamma + r; a
+ * valid row pushes R into the Welford statistics; rew = r / sqrt(m2 / n + 1e-8) clamped to
+ * +-clip once n >= 2, the raw r before; a done step resets that player's return (valid or not).
+ * players NULL: the single-player kernel (P must be 1, valid and all_rewards NULL); otherwise the
+ * per-player kernel, and with all_rewards the acting player's slot of each row becomes rew, the
+ * other slots stay.  valid NULL: every row counts.  stats3 = {mean, m2, count} as
+ * bppo_ret_norm_get gives them.  BPPO_ERR_ARG (before any HIP call) for T or N < 1, P outside
+ * 1..BPPO_MAX_PLAYERS or a NULL rew_raw / done / returns_state / stats3 / rew. */
+bppo_status bppo_debug_return_norm(int32_t T, int32_t N, int32_t P, double gamma, float clip,
+                                   const float *rew_raw /*[T,N]*/, const float *done /*[T,N]*/,
+                                   const int32_t *players /*[T,N] or NULL*/, const float *valid /*[T,N] or NULL*/,
+                                   double *returns_state /*[N,P] in/out*/, double *stats3 /*in/out*/,
+                                   float *rew /*[T,N] out*/, float *all_rewards /*[T,N,P] in/out or NULL*/);
 /* Parity hook of the evaluation loop's forward (host buffers): the actor logits of n_models
  * models' row groups.  Model k owns rows [gbase[k], gbase[k + 1]) of xc [gbase[n_models]][G + D]
  * ([priv | obs] rows, raw: a model's obs normalizer is applied as the loop applies it) and of

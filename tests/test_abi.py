@@ -145,6 +145,27 @@ def test_create_rejects_nets_over_16_layers_before_any_hip_call(so, preset, over
         L.lib().bppo_destroy(h)
 
 
+def test_debug_return_norm_rejects_bad_arguments_before_any_hip_call(so):
+    """bppo_debug_return_norm checks P (1..BPPO_MAX_PLAYERS), its sizes and its required
+    pointers before the first HIP call, so BPPO_ERR_ARG comes back without a GPU."""
+    import numpy as np
+    import bppo._lib as L
+    T, N = 3, 4
+    f = np.zeros(T * N, np.float32); pl = np.zeros(T * N, np.int32)
+    R = np.zeros(N * 6); st = np.zeros(3); allr = np.zeros(T * N * 6, np.float32)
+
+    def call(T=T, N=N, P=2, raw=f, done=f, players=pl, valid=None, R=R, st=st, rew=f, allr=allr):
+        p = [None if a is None else a.ctypes.data for a in (raw, done, players, valid, R, st, rew, allr)]
+        return L.lib().bppo_debug_return_norm(T, N, P, 0.99, 10.0, *p)
+
+    for bad in (dict(P=0), dict(P=-1), dict(P=7), dict(T=0), dict(N=0), dict(raw=None), dict(done=None),
+                dict(R=None), dict(st=None), dict(rew=None),
+                dict(players=None, P=2, allr=None),               # the single-player kernel is P = 1
+                dict(players=None, P=1, allr=None, valid=f),      # ... without valid
+                dict(players=None, P=1)):                         # ... or all_rewards
+        assert call(**bad) == L.ERR_ARG, bad
+
+
 def test_null_context_is_an_argument_error(so):
     """every setter checks its context before touching it (bppo_optimizer_set
     dereferenced a NULL ctx); no HIP call is made, so this runs without a GPU."""

@@ -98,9 +98,10 @@ def test_gae_rows_device_bit_exact(T, N):
 
 
 @pytest.mark.parametrize("P,T,N", [(2, 64, 2048), (3, 64, 2048), (4, 64, 2048), (4, 128, 32768), (6, 37, 1000),
-                                   (2, 129, 300), (1, 16, 64)])
+                                   (2, 129, 300), (1, 16, 64), (5, 40, 130), (6, 128, 64), (6, 129, 70)])
 def test_gae_multiplayer_device_bit_exact(P, T, N):
-    """k_gae_mp_seg (T <= 128: T split over the waves of a block) and k_gae_mp (longer T)"""
+    """k_gae_mp_seg (T <= 128: T split over the waves of a block; T = 128 its last) and
+    k_gae_mp (longer T; (6, 129, 70) is k_gae_mp<6>); advantages and returns"""
     torch = _torch()
     rng = np.random.default_rng(P)
     pl = rng.integers(0, P, (T, N)).astype(np.int32)
@@ -117,6 +118,7 @@ def test_gae_multiplayer_device_bit_exact(P, T, N):
     assert st == 0
     torch.cuda.synchronize()
     assert np.array_equal(adv.cpu().numpy().view(np.uint32), adv_o.view(np.uint32))
+    assert np.array_equal(ret.cpu().numpy().view(np.uint32), ret_o.view(np.uint32))
 
 
 def test_gae_mp_known_answers_on_device():
