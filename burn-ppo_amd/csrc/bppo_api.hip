@@ -138,15 +138,6 @@ static float powi_f32(float a, int b) {   // compiler-rt __powisf2 (Rust f32::po
     return recip ? 1.0f / r : r;
 }
 
-template <class T>
-static bppo_status dalloc(bppo_ctx *c, T **p, size_t n) {
-    *p = nullptr;
-    if (n == 0) return BPPO_OK;
-    BPPO_HIP(c, hipMalloc((void **)p, n * sizeof(T)));
-    BPPO_HIP(c, hipMemsetAsync(*p, 0, n * sizeof(T), c->stream));
-    return BPPO_OK;
-}
-
 extern "C" size_t bppo_config_size(void) { return sizeof(bppo_config); }
 extern "C" size_t bppo_update_metrics_size(void) { return sizeof(bppo_update_metrics); }
 extern "C" size_t bppo_episode_size(void) { return sizeof(bppo_episode); }
@@ -272,83 +263,81 @@ static bppo_status ctx_init(bppo_ctx *c, const bppo_config *cfg, int dev, void *
     const size_t np = c->net.n_params;
     const size_t TN = (size_t)c->T * c->N;
     c->adam_t.assign(2 * c->net.n_layers, 0);
-    TRY(dalloc(c, &c->d_params, np));
-    TRY(dalloc(c, &c->d_m1, np));
-    TRY(dalloc(c, &c->d_m2, np));
-    TRY(dalloc(c, &c->d_grad, np + 64));
+    BPPO_HIP(c, c->zalloc(&c->d_params, np));
+    BPPO_HIP(c, c->zalloc(&c->d_m1, np));
+    BPPO_HIP(c, c->zalloc(&c->d_m2, np));
+    BPPO_HIP(c, c->zalloc(&c->d_grad, np + 64));
     c->slab_rows = 256 * 8;   // one 8-wave (MFMA) or 4-wave block per CU, persistent over the minibatch
     c->relu_mfma = cfg->relu ? 1 : 0;
-    if (!c->wide) TRY(dalloc(c, &c->d_slab, c->slab_rows * (np + 64)));
-    TRY(dalloc(c, &c->d_cp, (size_t)4 * c->N));
-    TRY(dalloc(c, &c->d_steps, (size_t)c->N));
-    TRY(dalloc(c, &c->d_env_pos, (size_t)c->N));
-    TRY(dalloc(c, &c->d_ep_ret, (size_t)c->N * c->P));
-    TRY(dalloc(c, &c->d_ep_len, (size_t)c->N));
-    if (!c->wide) TRY(dalloc(c, &c->d_obs, TN * c->D));
-    TRY(dalloc(c, &c->d_rew, TN));
-    TRY(dalloc(c, &c->d_rew_raw, TN));
-    TRY(dalloc(c, &c->d_done, TN));
-    TRY(dalloc(c, &c->d_val, TN));
-    TRY(dalloc(c, &c->d_logp, TN));
-    TRY(dalloc(c, &c->d_adv, TN));
-    TRY(dalloc(c, &c->d_ret, TN));
-    TRY(dalloc(c, &c->d_act, TN));
-    if (!c->wide || cfg->normalize_returns) TRY(dalloc(c, &c->d_X, TN));
+    if (!c->wide) BPPO_HIP(c, c->zalloc(&c->d_slab, c->slab_rows * (np + 64)));
+    BPPO_HIP(c, c->zalloc(&c->d_cp, (size_t)4 * c->N));
+    BPPO_HIP(c, c->zalloc(&c->d_steps, (size_t)c->N));
+    BPPO_HIP(c, c->zalloc(&c->d_env_pos, (size_t)c->N));
+    BPPO_HIP(c, c->zalloc(&c->d_ep_ret, (size_t)c->N * c->P));
+    BPPO_HIP(c, c->zalloc(&c->d_ep_len, (size_t)c->N));
+    if (!c->wide) BPPO_HIP(c, c->zalloc(&c->d_obs, TN * c->D));
+    BPPO_HIP(c, c->zalloc(&c->d_rew, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_rew_raw, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_done, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_val, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_logp, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_adv, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_ret, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_act, TN));
+    if (!c->wide || cfg->normalize_returns) BPPO_HIP(c, c->zalloc(&c->d_X, TN));
     if (!c->wide && cfg->hidden_size == 64 && cfg->num_hidden == 2 && cfg->relu)
     {
-        TRY(dalloc(c, &c->d_gumbel, TN * 2));
-        TRY(dalloc(c, &c->d_rpool, (size_t)RPOOL_K * c->N));
-        TRY(dalloc(c, &c->d_rpos, (size_t)RPOOL_K * c->N));
+        BPPO_HIP(c, c->zalloc(&c->d_gumbel, TN * 2));
+        BPPO_HIP(c, c->zalloc(&c->d_rpool, (size_t)RPOOL_K * c->N));
+        BPPO_HIP(c, c->zalloc(&c->d_rpos, (size_t)RPOOL_K * c->N));
     }
-    TRY(dalloc(c, &c->d_on, (size_t)2 * c->D + 1));
-    if (!c->wide) TRY(dalloc(c, &c->d_obs_part, (size_t)c->N * 2 * c->D));
-    if (!c->wide) {   // VecEnv::step / get_observations scratch (freed by wide_free with the rest)
-        TRY(dalloc(c, &c->d_act_in, (size_t)c->N));
-        TRY(dalloc(c, &c->d_scr_r, (size_t)c->N));
-        TRY(dalloc(c, &c->d_bxc, (size_t)c->N * c->D));
-        BPPO_HIP(c, hipMalloc((void **)&c->d_scr_d, (size_t)c->N));
+    BPPO_HIP(c, c->zalloc(&c->d_on, (size_t)2 * c->D + 1));
+    if (!c->wide) BPPO_HIP(c, c->zalloc(&c->d_obs_part, (size_t)c->N * 2 * c->D));
+    if (!c->wide) {   // VecEnv::step / get_observations scratch (wide_init's otherwise)
+        BPPO_HIP(c, c->zalloc(&c->d_act_in, (size_t)c->N));
+        BPPO_HIP(c, c->zalloc(&c->d_scr_r, (size_t)c->N));
+        BPPO_HIP(c, c->zalloc(&c->d_bxc, (size_t)c->N * c->D));
+        BPPO_HIP(c, c->mem.alloc(&c->d_scr_d, (size_t)c->N));
     }
-    TRY(dalloc(c, &c->d_rn_returns, (size_t)c->N * c->P));
-    TRY(dalloc(c, &c->d_rn_stats, 4));
-    TRY(dalloc(c, &c->d_scan_agg, (TN + 4095) / 4096 + 1));
-    TRY(dalloc(c, &c->d_last_v, (size_t)c->N));
+    BPPO_HIP(c, c->zalloc(&c->d_rn_returns, (size_t)c->N * c->P));
+    BPPO_HIP(c, c->zalloc(&c->d_rn_stats, 4));
+    BPPO_HIP(c, c->zalloc(&c->d_scan_agg, (TN + 4095) / 4096 + 1));
+    BPPO_HIP(c, c->zalloc(&c->d_last_v, (size_t)c->N));
     // room for every episode a rollout can complete (one per env-step): the episode
     // summary then sums all of them (a smaller cap kept whichever episodes claimed
     // slots first); CartPole's integer returns sum exactly in f64, so its mean does not
     // depend on the order the waves claimed their record slots
     c->eps_cap = (int)std::min<size_t>((size_t)c->T * c->N + 4096, (size_t)INT32_MAX / 2);
-    TRY(dalloc(c, &c->d_eps, (size_t)c->eps_cap));
-    TRY(dalloc(c, &c->d_ep_count, 1));
-    TRY(dalloc(c, &c->d_ep_sum, ROLL_HOST_WORDS));   // [count, err] + the partial sums: one host slot's layout
-    TRY(dalloc(c, &c->d_err, 1));
-    TRY(dalloc(c, &c->d_perm_base, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_eps, (size_t)c->eps_cap));
+    BPPO_HIP(c, c->zalloc(&c->d_ep_count, 1));
+    BPPO_HIP(c, c->zalloc(&c->d_ep_sum, ROLL_HOST_WORDS));   // [count, err] + the partial sums: one host slot's layout
+    BPPO_HIP(c, c->zalloc(&c->d_err, 1));
+    BPPO_HIP(c, c->zalloc(&c->d_perm_base, TN));
     c->d_perm = c->d_perm_base;
-    TRY(dalloc(c, &c->d_perm_ep, TN * (size_t)cfg->num_epochs));
-    TRY(dalloc(c, &c->d_inv_ep, TN * (size_t)cfg->num_epochs));
-    TRY(dalloc(c, &c->d_advpart, (size_t)ADV_STREAM_BLOCKS * ADV_STREAM_MAXM * 4));
+    BPPO_HIP(c, c->zalloc(&c->d_perm_ep, TN * (size_t)cfg->num_epochs));
+    BPPO_HIP(c, c->zalloc(&c->d_inv_ep, TN * (size_t)cfg->num_epochs));
+    BPPO_HIP(c, c->zalloc(&c->d_advpart, (size_t)ADV_STREAM_BLOCKS * ADV_STREAM_MAXM * 4));
     // the context's only streams are the update stream, fy_stream and the engine's copy
     // stream: a third low-priority stream, even idle, made every device-bound run
     // 15-25 % slower outside the minibatch kernels (profiles/r06y/, r06z/)
     BPPO_HIP(c, make_side_stream(dev, &c->fy_stream));
     for (int e = 0; e < cfg->num_epochs && e < SHUF_MAX_EPOCHS; e++)
         BPPO_HIP(c, hipEventCreateWithFlags(&c->fy_ev[e], hipEventDisableTiming));
-    TRY(dalloc(c, &c->d_fy, 4 * TN));
-    TRY(dalloc(c, &c->d_scan, TN / 8192 + 2));
-    BPPO_HIP(c, fy_ranges_init(c->fyr, (uint32_t)TN));
-    TRY(dalloc(c, &c->d_red, 4 * 1024 + 64));
-    TRY(dalloc(c, &c->d_mb_stats, (size_t)4 * std::max(cfg->num_minibatches, 2)));
+    BPPO_HIP(c, c->zalloc(&c->d_fy, 4 * TN));
+    BPPO_HIP(c, c->zalloc(&c->d_scan, TN / 8192 + 2));
+    BPPO_HIP(c, fy_ranges_init(c->mem, c->fyr, (uint32_t)TN));
+    BPPO_HIP(c, c->zalloc(&c->d_red, 4 * 1024 + 64));
+    BPPO_HIP(c, c->zalloc(&c->d_mb_stats, (size_t)4 * std::max(cfg->num_minibatches, 2)));
     c->d_mb_cur = c->d_mb_stats;
-    TRY(dalloc(c, &c->d_rows, (size_t)cfg->num_epochs * cfg->num_minibatches * (WM_COUNT + 4)));
-    BPPO_HIP(c, hipHostMalloc((void **)&c->h_rows,
-                              sizeof(float) * (size_t)cfg->num_epochs * cfg->num_minibatches * (WM_COUNT + 4),
-                              hipHostMallocDefault));
+    BPPO_HIP(c, c->zalloc(&c->d_rows, (size_t)cfg->num_epochs * cfg->num_minibatches * (WM_COUNT + 4)));
+    BPPO_HIP(c, c->mem.alloc_pinned(&c->h_rows, (size_t)cfg->num_epochs * cfg->num_minibatches * (WM_COUNT + 4)));
     if (!c->wide && cfg->hidden_size == 64 && cfg->num_hidden == 2 && cfg->relu && c->D == 5)
     {
-        BPPO_HIP(c, hipMalloc((void **)&c->d_rowA, sizeof(float4) * 2 * TN));
-        BPPO_HIP(c, hipMalloc((void **)&c->d_rowB, sizeof(float2) * TN));
+        BPPO_HIP(c, c->mem.alloc(&c->d_rowA, 2 * TN));
+        BPPO_HIP(c, c->mem.alloc(&c->d_rowB, TN));
     }
-    BPPO_HIP(c, hipHostMalloc((void **)&c->h_red, sizeof(double) * (4 * 1024 + 64 + 2 * ROLL_HOST_WORDS),
-                              hipHostMallocDefault));   // + two slots of the rollout's flags and episode partials
+    // + two slots of the rollout's flags and episode partials
+    BPPO_HIP(c, c->mem.alloc_pinned(&c->h_red, (size_t)4 * 1024 + 64 + 2 * ROLL_HOST_WORDS));
     BPPO_HIP(c, hipEventCreateWithFlags(&c->ev_upd, hipEventDisableTiming));
     BPPO_HIP(c, hipEventRecord(c->ev_upd, c->stream));      // recorded once, so every wait on it is defined
     BPPO_HIP(c, hipEventCreateWithFlags(&c->ev_block, hipEventDisableTiming | hipEventBlockingSync));
@@ -394,22 +383,10 @@ extern "C" void bppo_destroy(bppo_ctx *c) {
     if (c->ev_stream) { (void)hipStreamSynchronize(c->ev_stream); (void)hipStreamDestroy(c->ev_stream); }
     if (c->ev_gae) (void)hipEventDestroy(c->ev_gae);
     if (c->ev_copied) (void)hipEventDestroy(c->ev_copied);
-    for (float *h : {c->h_ev_v, c->h_ev_r, c->h_ev_valid}) if (h) (void)hipHostFree(h);
     if (c->fy_stream) (void)hipStreamSynchronize(c->fy_stream);   // reads the engine's J buffers
     c->shuf.shutdown();
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    wide_free(c);
-    popart_free(c);
-    void *ptrs[] = {c->d_params, c->d_m1, c->d_m2, c->d_grad, c->d_slab, c->d_cp, c->d_steps,
-                    c->d_env_pos, c->d_ep_ret, c->d_ep_len, c->d_obs, c->d_rew, c->d_rew_raw,
-                    c->d_done, c->d_val, c->d_logp, c->d_adv, c->d_ret, c->d_act, c->d_X, c->d_on,
-                    c->d_obs_part, c->d_rn_returns, c->d_rn_stats, c->d_scan_agg, c->d_last_v,
-                    c->d_eps, c->d_ep_count, c->d_ep_sum, c->d_err, c->d_perm_base, c->d_perm_ep, c->d_inv_ep, c->d_advpart, c->d_fy, c->d_scan,
-                    c->d_red, c->d_mb_stats, c->d_gumbel, c->d_rpool, c->d_rpos, c->d_rows, c->d_rowA, c->d_rowB};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    fy_ranges_free(c->fyr);
-    if (c->h_red) (void)hipHostFree(c->h_red);
-    if (c->h_rows) (void)hipHostFree(c->h_rows);
+    c->mem.free_all();
     if (c->ev_block) (void)hipEventDestroy(c->ev_block);
     if (c->ev_upd) (void)hipEventDestroy(c->ev_upd);
     for (int i = 0; i < TM_SLOTS; i++) {
@@ -458,11 +435,11 @@ extern "C" bppo_status bppo_forward(bppo_ctx *c, const float *obs, const float *
     if (!c || !obs || B <= 0) return BPPO_ERR_ARG;
     if (c->wide) return wide_forward_host(c, obs, priv, B, logits, values);
     // scratch freed on every return path (an inference call, not the rollout path)
-    struct Scratch { float *p[3] = {nullptr, nullptr, nullptr}; ~Scratch() { for (float *q : p) (void)hipFree(q); } } t;
-    BPPO_HIP(c, hipMalloc((void **)&t.p[0], sizeof(float) * (size_t)B * c->D));
-    BPPO_HIP(c, hipMalloc((void **)&t.p[1], sizeof(float) * (size_t)B * c->A));
-    BPPO_HIP(c, hipMalloc((void **)&t.p[2], sizeof(float) * (size_t)B));
-    float *d_o = t.p[0], *d_l = t.p[1], *d_v = t.p[2];
+    DeviceMem mem;
+    float *d_o = nullptr, *d_l = nullptr, *d_v = nullptr;
+    BPPO_HIP(c, mem.alloc(&d_o, (size_t)B * c->D));
+    BPPO_HIP(c, mem.alloc(&d_l, (size_t)B * c->A));
+    BPPO_HIP(c, mem.alloc(&d_v, (size_t)B));
     BPPO_HIP(c, hipMemcpyAsync(d_o, obs, sizeof(float) * (size_t)B * c->D, hipMemcpyHostToDevice, c->stream));
     bppo_status s = launch_forward_rows(c, d_o, B, d_l, d_v);
     if (s == BPPO_OK) {
@@ -962,11 +939,11 @@ extern "C" bppo_status bppo_set_explained_variance_mode(bppo_ctx *c, int32_t mod
         hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&e_gae, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&e_cp, hipEventDisableTiming | hipEventBlockingSync);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&hv, TN * 4, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&hr, TN * 4, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&hm, TN * 4, hipHostMallocDefault);
+        if (e == hipSuccess) e = c->mem.alloc_pinned(&hv, TN);
+        if (e == hipSuccess) e = c->mem.alloc_pinned(&hr, TN);
+        if (e == hipSuccess) e = c->mem.alloc_pinned(&hm, TN);
         if (e != hipSuccess) {
-            for (float *h : {hv, hr, hm}) if (h) (void)hipHostFree(h);
+            (void)c->mem.release(hv); (void)c->mem.release(hr); (void)c->mem.release(hm);
             if (e_cp) (void)hipEventDestroy(e_cp);
             if (e_gae) (void)hipEventDestroy(e_gae);
             if (st) (void)hipStreamDestroy(st);
@@ -1377,8 +1354,8 @@ extern "C" bppo_status bppo_train_steps(bppo_ctx *c, int32_t n, const double *lr
 // scratch is sized for the world here
 static bppo_status check_world(bppo_ctx *c, int32_t world) {
     if (world > 1 && c->cfg.normalize_values) {
-        if (c->d_pa_gather) { BPPO_HIP(c, hipFree(c->d_pa_gather)); c->d_pa_gather = nullptr; }
-        BPPO_HIP(c, hipMalloc((void **)&c->d_pa_gather, sizeof(float) * 9 * (size_t)world));
+        BPPO_HIP(c, c->mem.release(c->d_pa_gather));
+        BPPO_HIP(c, c->mem.alloc(&c->d_pa_gather, 9 * (size_t)world));
     }
     return BPPO_OK;
 }
@@ -1540,14 +1517,14 @@ extern "C" bppo_status bppo_debug_libm(int32_t which, int32_t device, const floa
         }
         return BPPO_OK;
     }
+    DeviceMem mem;
     float *dx = nullptr, *dy = nullptr;
-    if (hipMalloc((void **)&dx, n * 4) != hipSuccess || hipMalloc((void **)&dy, n * 4) != hipSuccess) return BPPO_ERR_HIP;
+    if (mem.alloc(&dx, n) != hipSuccess || mem.alloc(&dy, n) != hipSuccess) return BPPO_ERR_HIP;
     bppo_status s = BPPO_ERR_HIP;
     if (hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice) == hipSuccess &&
         launch_libm(which, dx, dy, n) == BPPO_OK && hipDeviceSynchronize() == hipSuccess &&
         hipMemcpy(y, dy, n * 4, hipMemcpyDeviceToHost) == hipSuccess)
         s = BPPO_OK;
-    (void)hipFree(dx); (void)hipFree(dy);
     return s;
 }
 
@@ -1630,18 +1607,17 @@ extern "C" bppo_status bppo_debug_shuffle_engine(uint64_t seed, uint64_t stream,
 extern "C" bppo_status bppo_debug_fisher_yates(int32_t device, const uint32_t *J, uint32_t n, uint32_t *perm) {
     if (!J || !perm) return BPPO_ERR_ARG;
     if (hipSetDevice(device) != hipSuccess) return BPPO_ERR_HIP;
+    DeviceMem mem;
     uint32_t *dJ = nullptr, *dP = nullptr, *dS = nullptr, *dC = nullptr;
     FyRanges rg;
     bppo_status s = BPPO_ERR_HIP;
-    if (hipMalloc((void **)&dJ, 4ull * n + 4) == hipSuccess && hipMalloc((void **)&dP, 4ull * n + 4) == hipSuccess &&
-        hipMalloc((void **)&dS, 16ull * n + 16) == hipSuccess && hipMalloc((void **)&dC, 4ull * (n / 8192 + 2)) == hipSuccess &&
+    if (mem.alloc(&dJ, (size_t)n + 1) == hipSuccess && mem.alloc(&dP, (size_t)n + 1) == hipSuccess &&
+        mem.alloc(&dS, 4 * ((size_t)n + 1)) == hipSuccess && mem.alloc(&dC, (size_t)n / 8192 + 2) == hipSuccess &&
         hipMemcpy(dJ, J, 4ull * n, hipMemcpyHostToDevice) == hipSuccess &&
-        fy_ranges_init(rg, n) == hipSuccess &&
+        fy_ranges_init(mem, rg, n) == hipSuccess &&
         fisher_yates_device(dJ, n, dS, dC, dP, nullptr, &rg) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
         hipMemcpy(perm, dP, 4ull * n, hipMemcpyDeviceToHost) == hipSuccess)
         s = BPPO_OK;
-    (void)hipFree(dJ); (void)hipFree(dP); (void)hipFree(dS); (void)hipFree(dC);
-    fy_ranges_free(rg);
     return s;
 }
 
@@ -1661,11 +1637,12 @@ extern "C" bppo_status bppo_debug_sample(int32_t A, int32_t B, const float *logi
     std::vector<uint8_t> ones;
     if (!masks) { ones.assign(nA, 1); masks = ones.data(); }
     int32_t err = 0;
-    if (hipMalloc((void **)&d_l, nA * 4) == hipSuccess && hipMalloc((void **)&d_m, nA) == hipSuccess &&
-        hipMalloc((void **)&d_v, 4ull * B) == hipSuccess && hipMalloc((void **)&d_lp, 4ull * B) == hipSuccess &&
-        hipMalloc((void **)&d_val, 4ull * B) == hipSuccess && hipMalloc((void **)&d_lv, 4ull * B) == hipSuccess &&
-        hipMalloc((void **)&d_p, 4ull * B) == hipSuccess && hipMalloc((void **)&d_a, 4ull * B) == hipSuccess &&
-        hipMalloc((void **)&d_e, 4) == hipSuccess && hipMemset(d_v, 0, 4ull * B) == hipSuccess &&
+    DeviceMem mem;
+    if (mem.alloc(&d_l, nA) == hipSuccess && mem.alloc(&d_m, nA) == hipSuccess &&
+        mem.alloc(&d_v, (size_t)B) == hipSuccess && mem.alloc(&d_lp, (size_t)B) == hipSuccess &&
+        mem.alloc(&d_val, (size_t)B) == hipSuccess && mem.alloc(&d_lv, (size_t)B) == hipSuccess &&
+        mem.alloc(&d_p, (size_t)B) == hipSuccess && mem.alloc(&d_a, (size_t)B) == hipSuccess &&
+        mem.alloc(&d_e, 1) == hipSuccess && hipMemset(d_v, 0, 4ull * B) == hipSuccess &&
         hipMemset(d_p, 0, 4ull * B) == hipSuccess && hipMemset(d_e, 0, 4) == hipSuccess &&
         hipMemcpy(d_l, logits, nA * 4, hipMemcpyHostToDevice) == hipSuccess &&
         hipMemcpy(d_m, masks, nA, hipMemcpyHostToDevice) == hipSuccess) {
@@ -1679,7 +1656,13 @@ extern "C" bppo_status bppo_debug_sample(int32_t A, int32_t B, const float *logi
             hipMemcpy(&err, d_e, 4, hipMemcpyDeviceToHost) == hipSuccess)
             s = (err & 2) ? BPPO_ERR_EMPTY_MASK : (err & 1) ? BPPO_ERR_NONFINITE : BPPO_OK;
     }
-    void *ptrs[] = {d_l, d_m, d_v, d_lp, d_val, d_lv, d_p, d_a, d_e};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
     return s;
+}
+
+// live allocations and bytes of every DeviceMem of the process (no HIP call)
+extern "C" bppo_status bppo_debug_device_memory(int64_t *live_allocations, int64_t *live_bytes) {
+    if (!live_allocations || !live_bytes) return BPPO_ERR_ARG;
+    *live_allocations = DeviceMem::live_allocations.load();
+    *live_bytes = DeviceMem::live_bytes.load();
+    return BPPO_OK;
 }

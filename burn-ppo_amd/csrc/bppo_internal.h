@@ -75,6 +75,56 @@ struct OppResults {
 // Welford state (count, mean, M2) — Chan merge is the associative combine
 struct Welford { double n, mean, m2; };
 
+// --------------------------------------------------------------- memory -----
+// The one owner of device and pinned host memory outside the shuffle engine.  It
+// records what it hands out, release() returns one buffer early, free_all() (also
+// the destructor) the rest.  The counters cover every owner of the process
+// (bppo_debug_device_memory).
+struct DeviceMem {
+    struct Block { void *p; size_t bytes; bool pinned; };
+    std::vector<Block> blocks;
+    static inline std::atomic<int64_t> live_allocations{0}, live_bytes{0};
+    DeviceMem() = default;
+    DeviceMem(const DeviceMem &) = delete;
+    DeviceMem &operator=(const DeviceMem &) = delete;
+    ~DeviceMem() { free_all(); }
+    // n elements (at least one); *p is nullptr on failure
+    template <class T> hipError_t alloc(T **p, size_t n) { return take((void **)p, bytes_of<T>(n), false); }
+    template <class T> hipError_t alloc_pinned(T **p, size_t n) { return take((void **)p, bytes_of<T>(n), true); }
+    // ... zero-filled on st
+    template <class T> hipError_t alloc_zero(T **p, size_t n, hipStream_t st) {
+        const hipError_t e = alloc(p, n);
+        return e != hipSuccess ? e : hipMemsetAsync(*p, 0, bytes_of<T>(n), st);
+    }
+    template <class T> hipError_t release(T *&p) {
+        hipError_t e = hipSuccess;
+        for (size_t i = 0; i < blocks.size(); i++)
+            if (blocks[i].p == (void *)p) { e = drop(blocks[i]); blocks.erase(blocks.begin() + i); break; }
+        p = nullptr;
+        return e;
+    }
+    void free_all() {
+        for (const Block &b : blocks) (void)drop(b);
+        blocks.clear();
+    }
+private:
+    template <class T> static size_t bytes_of(size_t n) { return (n ? n : 1) * sizeof(T); }
+    hipError_t take(void **p, size_t bytes, bool pinned) {
+        *p = nullptr;
+        const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+        if (e != hipSuccess) { *p = nullptr; return e; }
+        blocks.push_back({*p, bytes, pinned});
+        live_allocations += 1;
+        live_bytes += (int64_t)bytes;
+        return hipSuccess;
+    }
+    static hipError_t drop(const Block &b) {
+        live_allocations -= 1;
+        live_bytes -= (int64_t)b.bytes;
+        return b.pinned ? hipHostFree(b.p) : hipFree(b.p);
+    }
+};
+
 // -------------------------------------------------------------- shuffle -----
 // rand 0.8.5 SliceRandom::shuffle (ppo.rs:1816) on the main StdRng.  The draw
 // chain (every draw may reject, so each draw's word position depends on all
@@ -265,6 +315,8 @@ struct bppo_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
+    bppo::DeviceMem mem;              // every device / pinned buffer below (the engine keeps its own)
+    template <class T> hipError_t zalloc(T **p, size_t n) { return mem.alloc_zero(p, n, stream); }   // zeroed on the stream
     int N = 0, T = 0, D = 0, A = 0, P = 1, G = 0;
     int Pa = 1;                       // players actually seated (Skull: player_count; else P)
     bppo::NetLayout net;
@@ -272,7 +324,6 @@ struct bppo_ctx {
     float *d_params = nullptr, *d_m1 = nullptr, *d_m2 = nullptr;
     std::vector<int32_t> adam_t;
     float *d_grad = nullptr;          // [n_params + metric slots]
-    double *d_grad64 = nullptr;
     float *d_slab = nullptr;          // per-wave partial gradients
     size_t slab_rows = 0;
     int slab_used = 0;                // waves that wrote a row in the last minibatch launch
@@ -504,8 +555,7 @@ bppo_status launch_return_norm(bppo_ctx *c);
 bppo_status launch_fisher_yates(bppo_ctx *c, const uint32_t *d_J, uint32_t n);
 hipError_t fisher_yates_device(const uint32_t *d_J, uint32_t n, uint32_t *scratch, uint32_t *scan, uint32_t *perm,
                                hipStream_t st, const FyRanges *rg, uint32_t *inv = nullptr);
-hipError_t fy_ranges_init(FyRanges &r, uint32_t n);
-void fy_ranges_free(FyRanges &r);
+hipError_t fy_ranges_init(DeviceMem &mem, FyRanges &r, uint32_t n);
 bppo_status launch_epoch_adv_stats(bppo_ctx *c, uint32_t B, int M, const uint32_t *inv = nullptr);
 bppo_status launch_minibatch(bppo_ctx *c, uint32_t start, uint32_t n, float ent_coef, bool exact);
 bppo_status launch_adam(bppo_ctx *c, float lr, const float *c1, const float *c2, float *metric_dst = nullptr,
@@ -516,7 +566,6 @@ bppo_status launch_explained_variance(bppo_ctx *c, const float *valid);
 void explained_variance_sums(bppo_ctx *c, double *out4);   // after the stream wait
 // (wide_api.hip) multi-player path
 bppo_status wide_init(bppo_ctx *c);
-void wide_free(bppo_ctx *c);
 bppo_status wide_reset(bppo_ctx *c);
 bppo_status wide_pack(bppo_ctx *c);
 bppo_status wide_forward(bppo_ctx *c, int rows, const float *xc, int ldxc, float *logits, float *values,
@@ -529,7 +578,6 @@ bppo_status wide_forward_actor_groups(bppo_ctx *c, const int32_t *gbase, const F
 // CNN trunk (cnn.hip): conv stack + flatten of `rows` obs rows -> d_cnn_f; backward
 // of the conv stack from dF (dL/d features, [rows][fdim]) into the gradient
 bppo_status cnn_alloc(bppo_ctx *c);
-void cnn_free(bppo_ctx *c);
 bppo_status cnn_pack(bppo_ctx *c, const float *params, float *wt, float *wd);
 bppo_status cnn_features(bppo_ctx *c, int s, int rows, const float *x, int ldx, const float *params, const float *wt);
 bppo_status cnn_backward(bppo_ctx *c, int s, int rows, const float *x, int ldx, float *dF, float *grad, int exact);
@@ -548,7 +596,6 @@ inline int wide_exact_grad(const bppo_ctx *c) {
 // opponent pool (opponents.hip)
 bool opp_active(const bppo_ctx *c);
 bppo_status opp_alloc(bppo_ctx *c);
-void opp_free(bppo_ctx *c);
 bppo_status opp_rollout_begin(bppo_ctx *c, uint64_t base);
 bppo_status opp_records_clear(bppo_ctx *c);   // no finished games, zero sums (stream-ordered)
 bppo_status opp_step_group(bppo_ctx *c, int t);
@@ -587,7 +634,6 @@ inline double schedule_get(const std::vector<double> &v, const std::vector<uint6
 // the shaping bonus the envs add this step: reward_shaping_coef.get(current_step) as f32
 inline float shaping_coef(const bppo_ctx *c) { return (float)schedule_get(c->shaping_v, c->shaping_s, c->env_step); }
 bppo_status popart_alloc(bppo_ctx *c);
-void popart_free(bppo_ctx *c);
 bppo_status popart_denorm(bppo_ctx *c, float *v, size_t n);
 bppo_status popart_update_begin(bppo_ctx *c, const float *valid);
 bppo_status popart_target_stats(bppo_ctx *c, int full_epochs, size_t rows_done, const float *valid);

@@ -24,12 +24,6 @@
 
 namespace bppo {
 
-#define CHIP(c, expr)                                                       \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) return hip_fail((c), _e, #expr);              \
-    } while (0)
-
 // F[b][c*HW + hw] = Y[b*HW + hw][c];  F[b][HW*Cl + j] = x[b*ldx + HW*C0 + j]
 __global__ void __launch_bounds__(256) k_cnn_flatten(int B, int HW, int Cl, int C0, int E,
                                                       const float *__restrict__ Y, const float *__restrict__ x,
@@ -86,27 +80,18 @@ bppo_status cnn_alloc(bppo_ctx *c) {
             wt += (size_t)n.in[l] * n.out[l];
             c->cnn_wd_off[s][l] = wd;
             wd += (size_t)n.in[l] * gemm_conv_tap_pad(n.out[l]);   // Cin*kk*cpad
-            CHIP(c, hipMalloc((void **)&c->d_cnn_y[s][l], R * n.out[l] * 4));
+            BPPO_HIP(c, c->mem.alloc(&c->d_cnn_y[s][l], R * n.out[l]));
         }
-        CHIP(c, hipMalloc((void **)&c->d_cnn_f[s], (size_t)c->rows_max * n.fdim * 4));
+        BPPO_HIP(c, c->mem.alloc(&c->d_cnn_f[s], (size_t)c->rows_max * n.fdim));
     }
     const size_t dy = std::max(R * cmax, (size_t)c->rows_max * n.fdim);
-    CHIP(c, hipMalloc((void **)&c->d_cnn_dy[0], dy * 4));
-    CHIP(c, hipMalloc((void **)&c->d_cnn_dy[1], dy * 4));
-    CHIP(c, hipMalloc((void **)&c->d_cnn_wt, wt * 4));
-    CHIP(c, hipMalloc((void **)&c->d_cnn_wd, wd * 4));
-    CHIP(c, hipMalloc((void **)&c->d_cnn_owt, wt * 4));
-    CHIP(c, hipMalloc((void **)&c->d_cnn_dwt, kmax * cmax * 4));
+    BPPO_HIP(c, c->mem.alloc(&c->d_cnn_dy[0], dy));
+    BPPO_HIP(c, c->mem.alloc(&c->d_cnn_dy[1], dy));
+    BPPO_HIP(c, c->mem.alloc(&c->d_cnn_wt, wt));
+    BPPO_HIP(c, c->mem.alloc(&c->d_cnn_wd, wd));
+    BPPO_HIP(c, c->mem.alloc(&c->d_cnn_owt, wt));
+    BPPO_HIP(c, c->mem.alloc(&c->d_cnn_dwt, kmax * cmax));
     return BPPO_OK;
-}
-
-void cnn_free(bppo_ctx *c) {
-    for (int s = 0; s < 2; s++) {
-        for (float *q : c->d_cnn_y[s]) if (q) (void)hipFree(q);
-        if (c->d_cnn_f[s]) (void)hipFree(c->d_cnn_f[s]);
-    }
-    void *p[] = {c->d_cnn_dy[0], c->d_cnn_dy[1], c->d_cnn_wt, c->d_cnn_wd, c->d_cnn_owt, c->d_cnn_dwt};
-    for (void *q : p) if (q) (void)hipFree(q);
 }
 
 // the conv weights of `params` as GEMM operands (after every params change): Wt
@@ -126,7 +111,7 @@ bppo_status cnn_pack(bppo_ctx *c, const float *params, float *wt, float *wd) {
                                    n.conv_cin[l], kk, cpad, params + n.w[lg], wd + c->cnn_wd_off[s][l]);
             }
         }
-    CHIP(c, hipGetLastError());
+    BPPO_HIP(c, hipGetLastError());
     return BPPO_OK;
 }
 
@@ -135,12 +120,12 @@ bppo_status cnn_features(bppo_ctx *c, int s, int rows, const float *x, int ldx, 
     const NetLayout &n = c->net;
     const int HW = n.H * n.W, l0 = n.conv_base(s);
     for (int l = 0; l < n.n_conv; l++)
-        CHIP(c, gemm_conv_fwd(c->stream, rows, n.out[l], n.conv_cin[l], n.ksize, l ? c->d_cnn_y[s][l - 1] : x,
-                              l ? 0 : ldx, wt + c->cnn_wt_off[s][l], params + n.b[l0 + l], c->d_cnn_y[s][l]));
+        BPPO_HIP(c, gemm_conv_fwd(c->stream, rows, n.out[l], n.conv_cin[l], n.ksize, l ? c->d_cnn_y[s][l - 1] : x,
+                                  l ? 0 : ldx, wt + c->cnn_wt_off[s][l], params + n.b[l0 + l], c->d_cnn_y[s][l]));
     const int Cl = n.out[n.n_conv - 1];
     hipLaunchKernelGGL(k_cnn_flatten, grid_for((size_t)rows * n.fdim), dim3(256), 0, c->stream, rows, HW, Cl, n.C, n.E,
                        (const float *)c->d_cnn_y[s][n.n_conv - 1], x, ldx, c->d_cnn_f[s]);
-    CHIP(c, hipGetLastError());
+    BPPO_HIP(c, hipGetLastError());
     return BPPO_OK;
 }
 
@@ -154,20 +139,20 @@ bppo_status cnn_backward(bppo_ctx *c, int s, int rows, const float *x, int ldx, 
     if (dF == dy) std::swap(dy, dy2);
     hipLaunchKernelGGL(k_cnn_unflatten, grid_for((size_t)M * n.out[last]), dim3(256), 0, c->stream, rows, HW,
                        n.out[last], n.fdim, (const float *)dF, dy);
-    CHIP(c, hipGetLastError());
+    BPPO_HIP(c, hipGetLastError());
     for (int l = last; l >= 0; l--) {
         const int K = n.in[l], Co = n.out[l];
         const float *src = l ? c->d_cnn_y[s][l - 1] : x;
         const int sp = gemm_wg_splits(K, Co, M);
-        CHIP(c, gemm_conv_wgrad(c->stream, rows, Co, n.conv_cin[l], n.ksize, src, l ? 0 : ldx, dy, c->d_part,
-                                c->d_colsum, c->d_cnn_dwt, grad + n.b[l0 + l], sp, exact));
+        BPPO_HIP(c, gemm_conv_wgrad(c->stream, rows, Co, n.conv_cin[l], n.ksize, src, l ? 0 : ldx, dy, c->d_part,
+                                    c->d_colsum, c->d_cnn_dwt, grad + n.b[l0 + l], sp, exact));
         hipLaunchKernelGGL(k_cnn_transpose, dim3((K * Co + 255) / 256), dim3(256), 0, c->stream, K, Co,
                            (const float *)c->d_cnn_dwt, grad + n.w[l0 + l]);
-        CHIP(c, hipGetLastError());
+        BPPO_HIP(c, hipGetLastError());
         if (l == 0) break;
         // the input gradient straight into the previous layer's NHWC rows, relu' applied
-        CHIP(c, gemm_conv_dx(c->stream, rows, n.conv_cin[l], Co, n.ksize, dy, c->d_cnn_wd + c->cnn_wd_off[s][l],
-                             c->d_cnn_y[s][l - 1], dy2));
+        BPPO_HIP(c, gemm_conv_dx(c->stream, rows, n.conv_cin[l], Co, n.ksize, dy, c->d_cnn_wd + c->cnn_wd_off[s][l],
+                                 c->d_cnn_y[s][l - 1], dy2));
         std::swap(dy, dy2);
     }
     return BPPO_OK;

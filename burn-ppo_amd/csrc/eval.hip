@@ -345,23 +345,6 @@ static std::vector<int32_t> generate_permutations(int n) {
     return out;
 }
 
-// device memory of one evaluation, freed when it ends
-struct EvalBuffers {
-    std::vector<void *> dev;
-    EvalHdr *h_hdr = nullptr;
-    template <class T>
-    hipError_t alloc(T **p, size_t n) {
-        *p = nullptr;
-        const hipError_t e = hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) dev.push_back(*p);
-        return e;
-    }
-    ~EvalBuffers() {
-        for (void *p : dev) (void)hipFree(p);
-        if (h_hdr) (void)hipHostFree(h_hdr);
-    }
-};
-
 struct HostMath {
     float expf(float v) const { return bppo_math::expf_glibc(v); }
 };
@@ -419,7 +402,7 @@ extern "C" bppo_status bppo_debug_eval_sample(int32_t device, int32_t A, int32_t
     int32_t nd = 0;
     for (int b = 0; b < B; b++) didx[b] = bppo_eval::temp_draws(temps[b]) ? nd++ : -1;
     const size_t nA = (size_t)B * A;
-    EvalBuffers buf;
+    DeviceMem buf;   // this call's buffers, freed when it ends
     float *d_l = nullptr, *d_t = nullptr;
     uint8_t *d_m = nullptr;
     int32_t *d_di = nullptr, *d_a = nullptr, *d_u = nullptr, *d_e = nullptr;
@@ -462,7 +445,7 @@ struct EvalModels {
     std::vector<double> on;
     bool any_norm = false;
 };
-static bppo_status upload_models(bppo_ctx *c, EvalBuffers &buf, EvalModels &m, int K, const float *params,
+static bppo_status upload_models(bppo_ctx *c, DeviceMem &buf, EvalModels &m, int K, const float *params,
                                  const double *norm_mean, const double *norm_m2, const double *norm_count,
                                  uint64_t random_models) {
     const int D = c->D;
@@ -559,7 +542,7 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
     const int nperm = (int)(perms.size() / (size_t)P);
     const size_t np = c->net.n_params;
 
-    EvalBuffers buf;
+    DeviceMem buf;   // this call's buffers, freed when it ends
     EvalState s{};
     int32_t *d_perm_tab = nullptr, *d_seat_model = nullptr, *d_slot_model = nullptr;
     float *d_oxc = nullptr, *d_ologits = nullptr;
@@ -594,7 +577,8 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
     BPPO_HIP(c, buf.alloc(&d_ologits, (size_t)N * A));
     BPPO_HIP(c, buf.alloc(&d_sink, (size_t)N));
     BPPO_HIP(c, buf.alloc(&d_games, (size_t)n_pods * cap));
-    BPPO_HIP(c, hipHostMalloc((void **)&buf.h_hdr, sizeof(EvalHdr)));
+    EvalHdr *h_hdr = nullptr;
+    BPPO_HIP(c, buf.alloc_pinned(&h_hdr, 1));
     s.n_pods = n_pods; s.E = E; s.P = P; s.K = K; s.nperm = nperm; s.num_games = cfg->num_games; s.cap = cap;
     s.temp = bppo_eval::TempSched{cfg->temp_initial, cfg->temp_final, cfg->temp_cutoff, cfg->temp_decay};
     s.perm_tab = d_perm_tab; s.seat_model = d_seat_model; s.slot_model = d_slot_model;
@@ -627,14 +611,14 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
         TRY(launch_check(c, "k_eval_group"));
         hipLaunchKernelGGL(k_eval_scan, dim3(1), dim3(EV_SCAN_THREADS), 0, c->stream, s);
         TRY(launch_check(c, "k_eval_scan"));
-        BPPO_HIP(c, hipMemcpyAsync(buf.h_hdr, s.hdr, sizeof(EvalHdr), hipMemcpyDeviceToHost, c->stream));
+        BPPO_HIP(c, hipMemcpyAsync(h_hdr, s.hdr, sizeof(EvalHdr), hipMemcpyDeviceToHost, c->stream));
         BPPO_HIP(c, hipStreamSynchronize(c->stream));
         return BPPO_OK;
     };
     TRY(observe_group());
     bppo_status st = BPPO_OK;
     for (int step = 0;; step++) {
-        const EvalHdr &h = *buf.h_hdr;
+        const EvalHdr &h = *h_hdr;
         if (h.unfinished == 0) break;              // every pod: num_games games or no active env (eval.rs:1670-1674)
         if (step >= cfg->max_steps) { c->err = who + ": max_steps exceeded before every pod had played num_games games"; st = BPPO_ERR_ARG; break; }
         const int32_t *gb = h.gbase;
@@ -684,7 +668,7 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
         if (ng > 0) std::memcpy(games + k * cap_per_pod, &h_games[k * cap], sizeof(bppo_eval_game) * (size_t)ng);
     }
     if (st != BPPO_OK) return st;
-    const int32_t err = buf.h_hdr->err;
+    const int32_t err = h_hdr->err;
     if (err & 8) { c->err = who + ": an action outside the env's action mask"; return BPPO_ERR_ARG; }
     if (err & EV_ERR_ZERO_SUM) { c->err = who + ": the sampler's softmax sum was zero"; return BPPO_ERR_NONFINITE; }
     return BPPO_OK;
@@ -787,7 +771,7 @@ extern "C" bppo_status bppo_debug_forward_groups(bppo_ctx *c, int32_t mode, int3
     if (rows == 0) return BPPO_OK;
     drop_prefetch(c);
     if (!c->gae_done) c->collected = 0;       // the hidden buffers are the rollout's
-    EvalBuffers buf;
+    DeviceMem buf;   // this call's buffers, freed when it ends
     EvalModels mod;
     int32_t *d_gb = nullptr;
     float *d_x = nullptr, *d_l = nullptr;

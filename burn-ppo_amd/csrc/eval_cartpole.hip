@@ -228,23 +228,6 @@ __global__ void __launch_bounds__(CE_THREADS) k_cartpole_eval(CpEvalArgs a) {
     }
 }
 
-// device and pinned memory of one call, freed when it ends
-struct CpEvalBuffers {
-    std::vector<void *> dev;
-    CpEvalHdr *h_hdr = nullptr;
-    template <class T>
-    hipError_t alloc(T **p, size_t n) {
-        *p = nullptr;
-        const hipError_t e = hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) dev.push_back(*p);
-        return e;
-    }
-    ~CpEvalBuffers() {
-        for (void *p : dev) (void)hipFree(p);
-        if (h_hdr) (void)hipHostFree(h_hdr);
-    }
-};
-
 static bppo_status launch_cartpole_eval(bppo_ctx *c, int n_pods, const CpEvalArgs &a) {
     const int h = c->cfg.hidden_size, nl = c->cfg.num_hidden;
     const dim3 grid(n_pods), blk(CE_THREADS);
@@ -313,7 +296,7 @@ extern "C" bppo_status bppo_evaluate_episodes(bppo_ctx *c, const bppo_eval_confi
         on[(size_t)k * 11 + 10] = norm_count[k];
     }
 
-    CpEvalBuffers buf;
+    DeviceMem buf;   // this call's buffers, freed when it ends
     CpEvalArgs a{};
     float *d_params = nullptr;
     double *d_on = nullptr;
@@ -326,7 +309,8 @@ extern "C" bppo_status bppo_evaluate_episodes(bppo_ctx *c, const bppo_eval_confi
     BPPO_HIP(c, buf.alloc(&a.env, N));
     BPPO_HIP(c, buf.alloc(&a.hdr, (size_t)n_pods));
     BPPO_HIP(c, buf.alloc(&a.games, (size_t)n_pods * cap));
-    BPPO_HIP(c, hipHostMalloc((void **)&buf.h_hdr, sizeof(CpEvalHdr) * (size_t)n_pods));
+    CpEvalHdr *h_hdr = nullptr;
+    BPPO_HIP(c, buf.alloc_pinned(&h_hdr, (size_t)n_pods));
     a.E = E; a.num_games = cfg->num_games; a.cap = cap; a.max_steps = cfg->max_steps; a.launch_steps = launch_steps;
     a.n_params = (int)np;
     a.temp = bppo_eval::TempSched{cfg->temp_initial, cfg->temp_final, cfg->temp_cutoff, cfg->temp_decay};
@@ -341,15 +325,15 @@ extern "C" bppo_status bppo_evaluate_episodes(bppo_ctx *c, const bppo_eval_confi
                        (const uint64_t *)d_base, a.env, a.hdr);
     TRY(launch_check(c, "k_cartpole_eval_init"));
     auto read_headers = [&]() -> bppo_status {
-        BPPO_HIP(c, hipMemcpyAsync(buf.h_hdr, a.hdr, sizeof(CpEvalHdr) * (size_t)n_pods, hipMemcpyDeviceToHost, c->stream));
+        BPPO_HIP(c, hipMemcpyAsync(h_hdr, a.hdr, sizeof(CpEvalHdr) * (size_t)n_pods, hipMemcpyDeviceToHost, c->stream));
         BPPO_HIP(c, hipStreamSynchronize(c->stream));
         return BPPO_OK;
     };
-    auto unfinished = [&](int k) { return buf.h_hdr[k].games < cfg->num_games && buf.h_hdr[k].active > 0; };
+    auto unfinished = [&](int k) { return h_hdr[k].games < cfg->num_games && h_hdr[k].active > 0; };
     TRY(read_headers());
     for (;;) {
         bool more = false;
-        for (int k = 0; k < n_pods; k++) more = more || (unfinished(k) && buf.h_hdr[k].steps < cfg->max_steps);
+        for (int k = 0; k < n_pods; k++) more = more || (unfinished(k) && h_hdr[k].steps < cfg->max_steps);
         if (!more) break;
         TRY(launch_cartpole_eval(c, n_pods, a));
         TRY(read_headers());
@@ -358,7 +342,7 @@ extern "C" bppo_status bppo_evaluate_episodes(bppo_ctx *c, const bppo_eval_confi
     bool over = false;
     int32_t err = 0;
     for (int k = 0; k < n_pods; k++) {
-        const CpEvalHdr &h = buf.h_hdr[k];
+        const CpEvalHdr &h = h_hdr[k];
         n_games[k] = h.games;
         if (rng_word_pos) rng_word_pos[k] = h.rngpos;
         if (loop_steps) loop_steps[k] = h.steps;

@@ -632,25 +632,26 @@ extern "C" bppo_status bppo_debug_return_norm(int32_t T, int32_t N, int32_t P, d
     double *d_ret = nullptr, *d_stats = nullptr, *d_X = nullptr;
     Welford *d_agg = nullptr;
     bppo_status s = BPPO_ERR_HIP;
+    DeviceMem mem;
     do {
-        if (hipMalloc((void **)&d_raw, n * 4) != hipSuccess || hipMalloc((void **)&d_done, n * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_rew, n * 4) != hipSuccess || hipMalloc((void **)&d_X, n * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&d_ret, nP * 8) != hipSuccess || hipMalloc((void **)&d_stats, 4 * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&d_agg, ((n + 4095) / 4096 + 1) * sizeof(Welford)) != hipSuccess) break;
+        if (mem.alloc(&d_raw, n) != hipSuccess || mem.alloc(&d_done, n) != hipSuccess) break;
+        if (mem.alloc(&d_rew, n) != hipSuccess || mem.alloc(&d_X, n) != hipSuccess) break;
+        if (mem.alloc(&d_ret, nP) != hipSuccess || mem.alloc(&d_stats, 4) != hipSuccess) break;
+        if (mem.alloc(&d_agg, (n + 4095) / 4096 + 1) != hipSuccess) break;
         if (hipMemcpy(d_raw, rew_raw, n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         if (hipMemcpy(d_done, done, n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         if (hipMemcpy(d_ret, returns_state, nP * 8, hipMemcpyHostToDevice) != hipSuccess) break;
         if (hipMemcpy(d_stats, stats3, 3 * 8, hipMemcpyHostToDevice) != hipSuccess) break;
         if (players) {
-            if (hipMalloc((void **)&d_pl, n * 4) != hipSuccess) break;
+            if (mem.alloc(&d_pl, n) != hipSuccess) break;
             if (hipMemcpy(d_pl, players, n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         }
         if (valid) {
-            if (hipMalloc((void **)&d_valid, n * 4) != hipSuccess) break;
+            if (mem.alloc(&d_valid, n) != hipSuccess) break;
             if (hipMemcpy(d_valid, valid, n * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         }
         if (all_rewards) {
-            if (hipMalloc((void **)&d_allr, n * P * 4) != hipSuccess) break;
+            if (mem.alloc(&d_allr, n * P) != hipSuccess) break;
             if (hipMemcpy(d_allr, all_rewards, n * P * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         }
         s = launch_return_norm_raw(T, N, P, gamma, clip, d_raw, d_done, d_pl, d_valid, d_ret, d_stats, d_X, d_agg,
@@ -664,7 +665,5 @@ extern "C" bppo_status bppo_debug_return_norm(int32_t T, int32_t N, int32_t P, d
         if (all_rewards && hipMemcpy(all_rewards, d_allr, n * P * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
         s = BPPO_OK;
     } while (0);
-    (void)hipFree(d_raw); (void)hipFree(d_done); (void)hipFree(d_valid); (void)hipFree(d_rew); (void)hipFree(d_allr);
-    (void)hipFree(d_pl); (void)hipFree(d_ret); (void)hipFree(d_stats); (void)hipFree(d_X); (void)hipFree(d_agg);
     return s;
 }

@@ -1153,13 +1153,14 @@ extern "C" bppo_status bppo_debug_gemm(int32_t mode, int32_t M, int32_t N, int32
     size_t nX = mode == 0 ? (size_t)N : (mode == 1 ? (size_t)M * N : 0);
     bppo_status s = BPPO_ERR_HIP;
     const int splits = mode == 2 ? gemm_wg_splits(M, N, K) : 1;
+    DeviceMem mem;
     do {
-        if (hipMalloc((void **)&dA, nA * 4) != hipSuccess || hipMalloc((void **)&dB, nB * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&dO, (size_t)M * N * 4) != hipSuccess) break;
+        if (mem.alloc(&dA, nA) != hipSuccess || mem.alloc(&dB, nB) != hipSuccess) break;
+        if (mem.alloc(&dO, (size_t)M * N) != hipSuccess) break;
         if (hipMemcpy(dA, A, nA * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         if (hipMemcpy(dB, B, nB * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         if (nX && bias_or_H) {
-            if (hipMalloc((void **)&dX, nX * 4) != hipSuccess) break;
+            if (mem.alloc(&dX, nX) != hipSuccess) break;
             if (hipMemcpy(dX, bias_or_H, nX * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         }
         hipError_t e;
@@ -1169,9 +1170,9 @@ extern "C" bppo_status bppo_debug_gemm(int32_t mode, int32_t M, int32_t N, int32
         } else if (mode == 1) {
             e = gemm_dx(nullptr, M, N, K, dA, K, dB, K, dX, N, act, dO, N, nullptr, 0, nullptr, split);
         } else {
-            if (hipMalloc((void **)&dO2, (size_t)N * 4) != hipSuccess) break;
-            if (hipMalloc((void **)&dP, (size_t)splits * M * N * 8) != hipSuccess) break;
-            if (hipMalloc((void **)&dC, (size_t)splits * N * 8) != hipSuccess) break;
+            if (mem.alloc(&dO2, (size_t)N) != hipSuccess) break;
+            if (mem.alloc(&dP, (size_t)splits * M * N * 2) != hipSuccess) break;   // f64 partials
+            if (mem.alloc(&dC, (size_t)splits * N * 2) != hipSuccess) break;
             e = gemm_wgrad(nullptr, M, N, K, dA, M, dB, N, dP, dC, dO, N, N, nullptr, 0, dO2, nullptr, splits, exact);
         }
         if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
@@ -1179,7 +1180,5 @@ extern "C" bppo_status bppo_debug_gemm(int32_t mode, int32_t M, int32_t N, int32
         if (mode == 2 && out2 && hipMemcpy(out2, dO2, (size_t)N * 4, hipMemcpyDeviceToHost) != hipSuccess) break;
         s = BPPO_OK;
     } while (0);
-    (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dX); (void)hipFree(dO); (void)hipFree(dO2);
-    (void)hipFree(dP); (void)hipFree(dC);
     return s;
 }

@@ -381,8 +381,8 @@ __global__ void __launch_bounds__(FY_DIRECT_THREADS) k_fy_direct_block(const uin
 static size_t fyb_lds(int nb, int ncb) { return sizeof(uint32_t) * (size_t)(2 * nb + 1 + ncb); }
 
 // range boundaries: equal expected load FYB_LOAD, at most FYB_RMAX targets each
-hipError_t fy_ranges_init(FyRanges &r, uint32_t n) {
-    fy_ranges_free(r);
+hipError_t fy_ranges_init(DeviceMem &mem, FyRanges &r, uint32_t n) {
+    r = FyRanges{};
     r.n = n;
     if (n < FYB_MIN_N) return hipSuccess;
     const double nd = (double)n;
@@ -413,31 +413,21 @@ hipError_t fy_ranges_init(FyRanges &r, uint32_t n) {
     }
     // the tables must fit in LDS
     if (fyb_lds(nb, (int)cb.size()) > FYB_LDS_MAX) return hipSuccess;
-    hipError_t e = hipMalloc((void **)&r.x, sizeof(uint32_t) * x.size());
-    if (e == hipSuccess) e = hipMalloc((void **)&r.cb, sizeof(uint32_t) * cb.size());
+    hipError_t e = mem.alloc(&r.x, x.size());
+    if (e == hipSuccess) e = mem.alloc(&r.cb, cb.size());
     // k_fyb_bucket's range slices, counts and overflow flag (zero: the invariant between
     // permutations that k_fyb_link and k_fy_direct_block restore)
     const size_t nbs = x.size() - 1;
-    if (e == hipSuccess) e = hipMalloc((void **)&r.P, sizeof(uint2) * nbs * FYB_CAP);
-    if (e == hipSuccess) e = hipMalloc((void **)&r.cursor, sizeof(uint32_t) * (nbs + 1));
+    if (e == hipSuccess) e = mem.alloc(&r.P, nbs * FYB_CAP);
+    if (e == hipSuccess) e = mem.alloc(&r.cursor, nbs + 1);
     if (e == hipSuccess) e = hipMemset(r.cursor, 0, sizeof(uint32_t) * (nbs + 1));
     r.flag = r.cursor ? r.cursor + nbs : nullptr;
     if (e == hipSuccess) e = hipMemcpy(r.x, x.data(), sizeof(uint32_t) * x.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(r.cb, cb.data(), sizeof(uint32_t) * cb.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { fy_ranges_free(r); return e; }
+    if (e != hipSuccess) return e;   // nb stays 0; the owner frees what was made
     r.nb = nb;
     r.ncb = (int)cb.size();
     return hipSuccess;
-}
-
-void fy_ranges_free(FyRanges &r) {
-    if (r.x) (void)hipFree(r.x);
-    if (r.cb) (void)hipFree(r.cb);
-    if (r.P) (void)hipFree(r.P);
-    if (r.cursor) (void)hipFree(r.cursor);
-    r.x = r.cb = r.cursor = r.flag = nullptr;
-    r.P = nullptr;
-    r.nb = r.ncb = 0;
 }
 
 // scratch: 4n u32 (counts, buckets, succ, fw); scan: n/8192 + 2 u32; perm: n u32

@@ -320,45 +320,24 @@ __global__ void k_map_perm(uint32_t n, const uint32_t *vidx, uint32_t *perm) {
 
 bool opp_active(const bppo_ctx *c) { return c->wide && c->n_opp > 0 && c->opp_K > 0; }
 
-void opp_free(bppo_ctx *c) {
-    void *ptrs[] = {c->d_opp_params, c->d_opp_on, c->d_lpos, c->d_p2o, c->d_curopp, c->d_group, c->d_gpos,
-                    c->d_valid, c->d_rngpos, c->d_oraw, c->d_oxc, c->d_ologits, c->d_vidx, c->d_Jopp, c->d_nvalid,
-                    c->d_gbase, c->d_opp_out, c->d_comp, c->d_opp_res};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (c->h_gbase) (void)hipHostFree(c->h_gbase);
-    c->h_gbase = nullptr; c->d_gbase = nullptr;
-    c->d_opp_params = nullptr; c->d_opp_on = nullptr; c->d_lpos = c->d_p2o = c->d_curopp = nullptr;
-    c->d_group = c->d_gpos = nullptr; c->d_valid = nullptr; c->d_rngpos = nullptr;
-    c->d_oraw = c->d_oxc = c->d_ologits = nullptr; c->d_vidx = c->d_Jopp = c->d_nvalid = nullptr;
-    c->d_opp_out = nullptr; c->d_comp = nullptr; c->d_opp_res = nullptr;
-}
-
-template <class T>
-static bppo_status oalloc(bppo_ctx *c, T **p, size_t n) {
-    if (*p) return BPPO_OK;
-    BPPO_HIP(c, hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    BPPO_HIP(c, hipMemsetAsync(*p, 0, std::max<size_t>(n, 1) * sizeof(T), c->stream));
-    return BPPO_OK;
-}
-
 bppo_status opp_alloc(bppo_ctx *c) {
     const size_t N = c->N, TN = (size_t)c->T * c->N;
-    TRY(oalloc(c, &c->d_group, N));
-    TRY(oalloc(c, &c->d_gpos, N));
-    TRY(oalloc(c, &c->d_valid, TN));
-    TRY(oalloc(c, &c->d_rngpos, 1));
-    TRY(oalloc(c, &c->d_oraw, N * c->L));
-    TRY(oalloc(c, &c->d_oxc, N * c->L));
-    TRY(oalloc(c, &c->d_ologits, N * c->A));
-    TRY(oalloc(c, &c->d_vidx, TN));
-    TRY(oalloc(c, &c->d_Jopp, TN));
-    TRY(oalloc(c, &c->d_nvalid, 1));
-    TRY(oalloc(c, &c->d_curopp, 4));
-    TRY(oalloc(c, &c->d_gbase, OPP_MAX_MODELS + 2));
-    if (!c->h_gbase) BPPO_HIP(c, hipHostMalloc((void **)&c->h_gbase, sizeof(int32_t) * (OPP_MAX_MODELS + 2)));
-    TRY(oalloc(c, &c->d_opp_out, N));
-    TRY(oalloc(c, &c->d_comp, (size_t)c->eps_cap));
-    TRY(oalloc(c, &c->d_opp_res, 1));
+    BPPO_HIP(c, c->zalloc(&c->d_group, N));
+    BPPO_HIP(c, c->zalloc(&c->d_gpos, N));
+    BPPO_HIP(c, c->zalloc(&c->d_valid, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_rngpos, 1));
+    BPPO_HIP(c, c->zalloc(&c->d_oraw, N * c->L));
+    BPPO_HIP(c, c->zalloc(&c->d_oxc, N * c->L));
+    BPPO_HIP(c, c->zalloc(&c->d_ologits, N * c->A));
+    BPPO_HIP(c, c->zalloc(&c->d_vidx, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_Jopp, TN));
+    BPPO_HIP(c, c->zalloc(&c->d_nvalid, 1));
+    BPPO_HIP(c, c->zalloc(&c->d_curopp, 4));
+    BPPO_HIP(c, c->zalloc(&c->d_gbase, OPP_MAX_MODELS + 2));
+    BPPO_HIP(c, c->mem.alloc_pinned(&c->h_gbase, OPP_MAX_MODELS + 2));
+    BPPO_HIP(c, c->zalloc(&c->d_opp_out, N));
+    BPPO_HIP(c, c->zalloc(&c->d_comp, (size_t)c->eps_cap));
+    BPPO_HIP(c, c->zalloc(&c->d_opp_res, 1));
     return BPPO_OK;
 }
 
@@ -491,22 +470,23 @@ extern "C" bppo_status bppo_opponents_set(bppo_ctx *c, int32_t n_models, const f
         for (int i = 0; i < P - 1; i++)
             if (current_opp[i] < 0 || current_opp[i] >= n_models) { c->err = "opponent pool: current_opp out of range"; return BPPO_ERR_ARG; }
     }
-    TRY(opp_alloc(c));
+    if (!c->d_opp_res) TRY(opp_alloc(c));   // once per context (d_opp_res is its last buffer)
     // the finished games on record were played under the seats and models replaced here
     TRY(opp_records_clear(c));
     BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
-    if (c->d_opp_params) { (void)hipFree(c->d_opp_params); c->d_opp_params = nullptr; }
-    if (c->d_opp_on) { (void)hipFree(c->d_opp_on); c->d_opp_on = nullptr; }
-    if (c->d_lpos) { (void)hipFree(c->d_lpos); c->d_lpos = nullptr; }
-    if (c->d_p2o) { (void)hipFree(c->d_p2o); c->d_p2o = nullptr; }
+    // the buffers sized by this call
+    (void)c->mem.release(c->d_opp_params);
+    (void)c->mem.release(c->d_opp_on);
+    (void)c->mem.release(c->d_lpos);
+    (void)c->mem.release(c->d_p2o);
     c->opp_K = n_models;
     c->n_opp = num_opponent_envs;
     c->opp_has_norm.assign(std::max(n_models, 1), 0);
-    TRY(oalloc(c, &c->d_opp_params, np * std::max(n_models, 1)));
-    TRY(oalloc(c, &c->d_opp_on, (size_t)(2 * D + 1) * std::max(n_models, 1)));
-    TRY(oalloc(c, &c->d_lpos, (size_t)std::max(num_opponent_envs, 1)));
-    TRY(oalloc(c, &c->d_p2o, (size_t)std::max(num_opponent_envs, 1) * P));
-    // uploads are ordered on the context stream after oalloc's zeroing memsets (a
+    BPPO_HIP(c, c->zalloc(&c->d_opp_params, np * std::max(n_models, 1)));
+    BPPO_HIP(c, c->zalloc(&c->d_opp_on, (size_t)(2 * D + 1) * std::max(n_models, 1)));
+    BPPO_HIP(c, c->zalloc(&c->d_lpos, (size_t)std::max(num_opponent_envs, 1)));
+    BPPO_HIP(c, c->zalloc(&c->d_p2o, (size_t)std::max(num_opponent_envs, 1) * P));
+    // uploads are ordered on the context stream after the allocations' zeroing memsets (a
     // blocking hipMemcpy on the null stream would not wait for that non-blocking
     // stream); the stream is drained before the host arrays may go away
     if (n_models > 0)

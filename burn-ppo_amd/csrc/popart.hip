@@ -26,17 +26,6 @@
 
 namespace bppo {
 
-#define PTRY(x)                                \
-    do {                                       \
-        bppo_status _s = (x);                  \
-        if (_s != BPPO_OK) return _s;          \
-    } while (0)
-#define PHIP(c, expr)                                                       \
-    do {                                                                    \
-        hipError_t _e = (expr);                                             \
-        if (_e != hipSuccess) return hip_fail((c), _e, #expr);              \
-    } while (0)
-
 double popart_std(const bppo_ctx *c) {          // normalization.rs:299-305
     return c->pa_count < 2.0 ? 1.0 : std::sqrt(c->pa_m2 / c->pa_count + c->pa_eps);
 }
@@ -122,23 +111,16 @@ static dim3 pgrid(size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) /
 bppo_status popart_denorm(bppo_ctx *c, float *v, size_t n) {
     if (!c->cfg.normalize_values || c->pa_count < 2.0 || n == 0) return BPPO_OK;
     hipLaunchKernelGGL(k_popart_denorm, pgrid(n), dim3(256), 0, c->stream, n, v, c->pa_mean, popart_std(c));
-    PHIP(c, hipGetLastError());
+    BPPO_HIP(c, hipGetLastError());
     return BPPO_OK;
 }
 
 bppo_status popart_alloc(bppo_ctx *c) {
     const size_t TN = (size_t)c->T * c->N;
-    PHIP(c, hipMalloc((void **)&c->d_ret_n, TN * 4));
-    PHIP(c, hipMalloc((void **)&c->d_val_n, TN * 4));
-    PHIP(c, hipMalloc((void **)&c->d_pa_part, sizeof(Welford) * PA_BLOCKS));   // >= 2 x 256 doubles of k_popart_sums
+    BPPO_HIP(c, c->mem.alloc(&c->d_ret_n, TN));
+    BPPO_HIP(c, c->mem.alloc(&c->d_val_n, TN));
+    BPPO_HIP(c, c->mem.alloc(&c->d_pa_part, sizeof(Welford) / sizeof(double) * PA_BLOCKS));   // >= 2 x 256 doubles of k_popart_sums
     return BPPO_OK;
-}
-
-void popart_free(bppo_ctx *c) {
-    if (c->d_ret_n) (void)hipFree(c->d_ret_n);
-    if (c->d_val_n) (void)hipFree(c->d_val_n);
-    if (c->d_pa_part) (void)hipFree(c->d_pa_part);
-    if (c->d_pa_gather) (void)hipFree(c->d_pa_gather);
 }
 
 static void chan_merge(Welford &a, const Welford &b) {
@@ -177,14 +159,14 @@ static bppo_status popart_gather(bppo_ctx *c, const std::vector<Welford> &part, 
     split3(mine.n, &g[9 * c->rank]); split3(mine.mean, &g[9 * c->rank + 3]); split3(mine.m2, &g[9 * c->rank + 6]);
     float own[9];
     std::memcpy(own, &g[9 * c->rank], sizeof own);
-    PHIP(c, hipMemcpyAsync(c->d_pa_gather, g.data(), g.size() * 4, hipMemcpyHostToDevice, c->stream));
-    if (!c->allreduce_async) PHIP(c, hipStreamSynchronize(c->stream));
+    BPPO_HIP(c, hipMemcpyAsync(c->d_pa_gather, g.data(), g.size() * 4, hipMemcpyHostToDevice, c->stream));
+    if (!c->allreduce_async) BPPO_HIP(c, hipStreamSynchronize(c->stream));
     if (c->allreduce(c->d_pa_gather, g.size(), c->allreduce_user) != 0) {
         c->err = "all-reduce callback failed (PopArt statistics)";
         return BPPO_ERR_COMM;
     }
-    PHIP(c, hipMemcpyAsync(g.data(), c->d_pa_gather, g.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    PHIP(c, hipStreamSynchronize(c->stream));
+    BPPO_HIP(c, hipMemcpyAsync(g.data(), c->d_pa_gather, g.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    BPPO_HIP(c, hipStreamSynchronize(c->stream));
     // two contexts given one rank: the slot they share holds a sum (checked by each of them),
     // and on the self-play path some other slot stays empty (seen by every rank alike)
     if (std::memcmp(own, &g[9 * c->rank], sizeof own) != 0) {
@@ -209,13 +191,13 @@ bppo_status popart_update_begin(bppo_ctx *c, const float *valid) {
     if (!c->cfg.normalize_values) return BPPO_OK;
     hipLaunchKernelGGL(k_popart_stats, dim3(PA_BLOCKS), dim3(256), 0, c->stream, TN, c->d_ret, valid,
                        (Welford *)c->d_pa_part);
-    PHIP(c, hipGetLastError());
+    BPPO_HIP(c, hipGetLastError());
     std::vector<Welford> part(PA_BLOCKS);
-    PHIP(c, hipMemcpyAsync(part.data(), c->d_pa_part, sizeof(Welford) * PA_BLOCKS, hipMemcpyDeviceToHost, c->stream));
-    PHIP(c, hipStreamSynchronize(c->stream));
+    BPPO_HIP(c, hipMemcpyAsync(part.data(), c->d_pa_part, sizeof(Welford) * PA_BLOCKS, hipMemcpyDeviceToHost, c->stream));
+    BPPO_HIP(c, hipStreamSynchronize(c->stream));
     const double old_mean = c->pa_mean, old_std = popart_std(c);
     Welford a{c->pa_count, c->pa_mean, c->pa_m2};
-    if (c->world > 1 && c->allreduce) PTRY(popart_gather(c, part, a, valid == nullptr));
+    if (c->world > 1 && c->allreduce) TRY(popart_gather(c, part, a, valid == nullptr));
     else
         for (const Welford &b : part) chan_merge(a, b);   // Chan merge in block (= row) order
     c->pa_count = a.n; c->pa_mean = a.mean; c->pa_m2 = a.m2;
@@ -225,15 +207,15 @@ bppo_status popart_update_begin(bppo_ctx *c, const float *valid) {
         const int len = n.in[n.value];
         hipLaunchKernelGGL(k_popart_rescale, dim3((len + 255) / 256), dim3(256), 0, c->stream, c->d_params, n.w[n.value],
                            len, n.b[n.value], old_std / new_std, old_std, old_mean, new_mean, new_std);
-        PHIP(c, hipGetLastError());
+        BPPO_HIP(c, hipGetLastError());
         c->pa_rescale_mag = (float)std::fabs(old_std / new_std);
-        if (c->wide) PTRY(wide_pack(c));
+        if (c->wide) TRY(wide_pack(c));
         const double sd = new_std;
         hipLaunchKernelGGL(k_popart_normalize, pgrid(TN), dim3(256), 0, c->stream, TN, (const float *)c->d_ret, c->d_ret_n,
                            new_mean, sd);
         hipLaunchKernelGGL(k_popart_normalize, pgrid(TN), dim3(256), 0, c->stream, TN, (const float *)c->d_val, c->d_val_n,
                            new_mean, sd);
-        PHIP(c, hipGetLastError());
+        BPPO_HIP(c, hipGetLastError());
         c->u_ret = c->d_ret_n; c->u_val = c->d_val_n;
     }
     return BPPO_OK;
@@ -251,15 +233,15 @@ bppo_status popart_target_stats(bppo_ctx *c, int full_epochs, size_t rows_done, 
         s1 = s2 = 0.0;
         if (!n) return BPPO_OK;
         hipLaunchKernelGGL(k_popart_sums, dim3(256), dim3(256), 0, c->stream, n, c->u_ret, idx, vf, c->d_pa_part);
-        PHIP(c, hipGetLastError());
-        PHIP(c, hipMemcpyAsync(h.data(), c->d_pa_part, sizeof(double) * 512, hipMemcpyDeviceToHost, c->stream));
-        PHIP(c, hipStreamSynchronize(c->stream));
+        BPPO_HIP(c, hipGetLastError());
+        BPPO_HIP(c, hipMemcpyAsync(h.data(), c->d_pa_part, sizeof(double) * 512, hipMemcpyDeviceToHost, c->stream));
+        BPPO_HIP(c, hipStreamSynchronize(c->stream));
         for (int b = 0; b < 256; b++) { s1 += h[2 * b]; s2 += h[2 * b + 1]; }
         return BPPO_OK;
     };
     double a1 = 0, a2 = 0, b1 = 0, b2 = 0;
-    if (full_epochs > 0) PTRY(sums(TN, nullptr, valid, a1, a2));
-    if (rows_done) PTRY(sums(rows_done, c->d_perm, nullptr, b1, b2));
+    if (full_epochs > 0) TRY(sums(TN, nullptr, valid, a1, a2));
+    if (rows_done) TRY(sums(rows_done, c->d_perm, nullptr, b1, b2));
     const double rows_all = valid ? (double)c->n_valid : (double)TN;
     c->pa_tsum = full_epochs * a1 + b1;
     c->pa_tsq = full_epochs * a2 + b2;

@@ -539,6 +539,7 @@ struct bppo_ratings {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
+    bppo::DeviceMem mem;               // the device and pinned buffers below
     // host mirror of the games [h_games][6]: complete for add_games; games appended on the
     // device by add_completions are fetched when a host fit (or a later add_games) needs them
     std::vector<int32_t> h_players, h_places;
@@ -598,10 +599,10 @@ bppo_status grow(bppo_ratings *r, T **p, int64_t *cap, int64_t need, int64_t kee
     if (need <= *cap) return BPPO_OK;
     const int64_t ncap = std::max<int64_t>(need, std::max<int64_t>(*cap * 2, 1024));
     T *q = nullptr;
-    RHIP(r, hipMalloc((void **)&q, sizeof(T) * (size_t)ncap * width));
+    RHIP(r, r->mem.alloc(&q, (size_t)ncap * width));
     if (*p && keep > 0) RHIP(r, hipMemcpyAsync(q, *p, sizeof(T) * (size_t)keep * width, hipMemcpyDeviceToDevice, r->stream));
     RHIP(r, hipStreamSynchronize(r->stream));
-    if (*p) RHIP(r, hipFree(*p));
+    RHIP(r, r->mem.release(*p));
     *p = q;
     *cap = ncap;
     return BPPO_OK;
@@ -847,18 +848,13 @@ extern "C" size_t bppo_pl_stats_size(void) { return sizeof(bppo_pl_stats); }
 
 extern "C" void bppo_ratings_destroy(bppo_ratings *r) {
     if (!r) return;
-    if (r->dev >= 0) {
-        (void)hipSetDevice(r->dev);
-        if (r->stream) (void)hipStreamSynchronize(r->stream);
-        void *ps[] = {r->d_players, r->d_places, r->d_w, r->d_cids, r->d_cw, r->d_gp, r->d_cnt, r->d_goff, r->d_meta,
-                      r->d_vec, r->d_list, r->d_off, r->d_total, r->d_hist, r->d_cval, r->d_H};
-        for (void *p : ps)
-            if (p) (void)hipFree(p);
-        if (r->h_meta) (void)hipHostFree(r->h_meta);
-        if (r->h_status) (void)hipHostFree(r->h_status);
-        if (r->ev) (void)hipEventDestroy(r->ev);
-        if (r->own_stream && r->stream) (void)hipStreamDestroy(r->stream);
-    }
+    // a host-only table holds none of these (no HIP call); one whose device initialisation
+    // failed part-way (dev -2) gives back what it got
+    if (r->dev >= 0) (void)hipSetDevice(r->dev);
+    if (r->stream) (void)hipStreamSynchronize(r->stream);
+    r->mem.free_all();
+    if (r->ev) (void)hipEventDestroy(r->ev);
+    if (r->own_stream && r->stream) (void)hipStreamDestroy(r->stream);
     delete r;
 }
 
@@ -869,13 +865,13 @@ static bppo_status ratings_init_device(bppo_ratings *r, void *hip_stream) {
         RHIP(r, hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
         r->own_stream = true;
     }
-    RHIP(r, hipMalloc((void **)&r->d_gp, sizeof(int32_t) * MAXN));
-    RHIP(r, hipMalloc((void **)&r->d_meta, sizeof(Meta)));
-    RHIP(r, hipMalloc((void **)&r->d_vec, sizeof(double) * (4 * MAXN + 2)));
-    RHIP(r, hipMalloc((void **)&r->d_off, sizeof(int32_t) * (MAXN + 1)));
-    RHIP(r, hipMalloc((void **)&r->d_total, sizeof(int32_t) * MAXN));
-    RHIP(r, hipHostMalloc((void **)&r->h_meta, sizeof(Meta)));
-    RHIP(r, hipHostMalloc((void **)&r->h_status, 2 * sizeof(double)));
+    RHIP(r, r->mem.alloc(&r->d_gp, MAXN));
+    RHIP(r, r->mem.alloc(&r->d_meta, 1));
+    RHIP(r, r->mem.alloc(&r->d_vec, 4 * MAXN + 2));
+    RHIP(r, r->mem.alloc(&r->d_off, MAXN + 1));
+    RHIP(r, r->mem.alloc(&r->d_total, MAXN));
+    RHIP(r, r->mem.alloc_pinned(&r->h_meta, 1));
+    RHIP(r, r->mem.alloc_pinned(&r->h_status, 2));
     RHIP(r, hipEventCreateWithFlags(&r->ev, hipEventDisableTiming));
     RHIP(r, hipMemsetAsync(r->d_gp, 0, sizeof(int32_t) * MAXN, r->stream));
     RHIP(r, hipStreamSynchronize(r->stream));

@@ -574,6 +574,12 @@ bppo_status bppo_last_kernel_ms(bppo_ctx *ctx, const char *kernel, float *ms);
  * device = 0 runs the host build of the same source, 1 runs the HIP kernel */
 bppo_status bppo_debug_libm(int32_t which, int32_t device, const float *x, float *y, size_t n);
 
+/* Device and pinned host allocations the library holds in this process, and their bytes
+ * (contexts, rating tables and calls in flight; not the shuffle engine's own buffers).
+ * No HIP call: works without a GPU.  Both return to their earlier values when what was
+ * created since is destroyed. */
+bppo_status bppo_debug_device_memory(int64_t *live_allocations, int64_t *live_bytes);
+
 /* shuffle parity hooks (ppo.rs:1816, rand 0.8.5 SliceRandom::shuffle on StdRng):
  * the host draw chain alone — J[i] = gen_range(0..i+1) for i = n-1..1 from word
  * position word_pos of StdRng(seed) stream `stream`, *end_pos = position after —

@@ -4,6 +4,7 @@ import ctypes as C
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -55,6 +56,19 @@ def test_host_libm_path_without_gpu():
     y = np.zeros_like(x)
     assert L.lib().bppo_debug_libm(0, 0, x.ctypes.data, y.ctypes.data, x.size) == 0
     assert np.allclose(y, np.log(x), rtol=1e-6, atol=1e-7)
+
+
+def test_device_memory_counters_start_at_zero(so):
+    """bppo_debug_device_memory makes no HIP call; a fresh process that has created nothing
+    holds no allocation and no byte"""
+    code = ("import sys, ctypes as C; sys.path.insert(0, sys.argv[1]); import bppo._lib as L; "
+            "a, b = C.c_int64(-1), C.c_int64(-1); "
+            "print(L.lib().bppo_debug_device_memory(C.byref(a), C.byref(b)), a.value, b.value)")
+    out = subprocess.run([sys.executable, "-c", code, os.path.join(ROOT, "burn-ppo_amd")], capture_output=True,
+                         text=True, check=True).stdout
+    assert out.split() == ["0", "0", "0"], out
+    import bppo._lib as L
+    assert L.lib().bppo_debug_device_memory(None, None) == L.ERR_ARG
 
 
 # ------------------------------------------------------------ struct layouts ---
