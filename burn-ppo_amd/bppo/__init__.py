@@ -12,6 +12,8 @@ from .tournament import (Contestant, DeviceEngine, TournamentResult, assign_byes
 from .host import make_config, minibatch_sizes, orthogonal_init, schedule_get  # noqa: F401
 from .ppo import (ActorCritic, Context, RolloutBuffer, Trainer, VecEnv, collect_rollouts,  # noqa: F401
                   compute_gae, perf_scalars, ppo_update, rollout_episodes, train_step)
+from .episodes import (EpisodeWindow, debug_episode_stats, episode_stats, rollout_episode_outcomes,  # noqa: F401
+                       set_episode_stats)
 from .pool import OpponentPool, OpponentStats, PoolTrainer, RatingHistory  # noqa: F401
 from .ratings import (PlackettLuceConfig, PlayerRating, RatingResult, RatingStats, RatingTable,  # noqa: F401
                       compute_ratings)

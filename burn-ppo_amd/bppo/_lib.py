@@ -49,6 +49,24 @@ class Episode(C.Structure):
                 ("step", C.c_int32), ("pad", C.c_int32)]
 
 
+class EpisodeStats(C.Structure):
+    """bppo_episode_stats: one rollout's finished episodes as mergeable statistics"""
+    _fields_ = [("episodes", C.c_int32), ("kept", C.c_int32), ("length_min", C.c_int32), ("length_max", C.c_int32),
+                ("length_sum", C.c_int64), ("with_outcome", C.c_int32), ("draws", C.c_int32),
+                ("return_sum", C.c_double * MAX_PLAYERS), ("return_min", C.c_float * MAX_PLAYERS),
+                ("return_max", C.c_float * MAX_PLAYERS), ("outcome_games", C.c_int32 * MAX_PLAYERS),
+                ("points2_sum", C.c_int64 * MAX_PLAYERS)]
+
+
+EPISODE_TAIL = 100
+
+
+class EpisodeTail(C.Structure):
+    """bppo_episode_tail: one episode of the last-100 window"""
+    _fields_ = [("total_reward", C.c_float * MAX_PLAYERS), ("placement", C.c_int32 * MAX_PLAYERS),
+                ("length", C.c_int32), ("env_index", C.c_int32), ("step", C.c_int32), ("has_outcome", C.c_int32)]
+
+
 class RolloutInfo(C.Structure):
     _fields_ = [("episodes", C.c_int32), ("mean_return", C.c_float), ("mean_length", C.c_float),
                 ("pad", C.c_int32), ("rng_word_pos", C.c_uint64)]
@@ -125,6 +143,8 @@ EXPORTS = (
     "bppo_ratings_add_games", "bppo_ratings_add_completions", "bppo_ratings_num_games", "bppo_ratings_fit",
     "bppo_ratings_last_fit_phases",
     "bppo_pl_config_size", "bppo_pl_stats_size",
+    "bppo_rollout_episode_outcomes", "bppo_set_episode_stats", "bppo_episode_stats_get",
+    "bppo_episode_stats_size", "bppo_episode_tail_size", "bppo_debug_episode_stats",
 )
 
 # ABI struct -> the library's sizeof export (checked when the library loads)
@@ -132,7 +152,8 @@ STRUCT_SIZES = {"bppo_config_size": Config, "bppo_update_metrics_size": UpdateMe
                 "bppo_episode_size": Episode, "bppo_rollout_info_size": RolloutInfo,
                 "bppo_eval_config_size": EvalConfig, "bppo_eval_game_size": EvalGame,
                 "bppo_opp_completion_size": OppCompletion,
-                "bppo_pl_config_size": PlConfig, "bppo_pl_stats_size": PlStats}
+                "bppo_pl_config_size": PlConfig, "bppo_pl_stats_size": PlStats,
+                "bppo_episode_stats_size": EpisodeStats, "bppo_episode_tail_size": EpisodeTail}
 
 _lib = None
 
@@ -178,6 +199,11 @@ def lib():
         "bppo_ret_norm_set": (i32, [vp, vp, vp]),
         "bppo_collect_rollouts": (i32, [vp, C.POINTER(RolloutInfo)]),
         "bppo_rollout_episodes": (i32, [vp, vp, i32, C.POINTER(i32)]),
+        "bppo_rollout_episode_outcomes": (i32, [vp, vp, vp, i32, C.POINTER(i32)]),
+        "bppo_set_episode_stats": (i32, [vp, i32]),
+        "bppo_episode_stats_get": (i32, [vp, i32, C.POINTER(EpisodeStats), vp, i32, C.POINTER(i32)]),
+        "bppo_debug_episode_stats": (i32, [i32, i32, vp, vp, i32, i32, i32, C.POINTER(EpisodeStats), vp,
+                                           C.POINTER(i32)]),
         "bppo_compute_gae": (i32, [vp]),
         "bppo_ppo_update": (i32, [vp, C.c_double, C.c_double, C.POINTER(UpdateMetrics)]),
         "bppo_train_step": (i32, [vp, C.c_double, C.c_double, C.POINTER(RolloutInfo), C.POINTER(UpdateMetrics)]),

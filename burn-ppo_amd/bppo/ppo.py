@@ -438,7 +438,7 @@ class Trainer:
     """run_training's per-update loop body (main.rs:684-988) on one GPU (or one
     rank of a data-parallel job)."""
 
-    def __init__(self, cfg=None, device=0, params=None, init_seed=0, **kw):
+    def __init__(self, cfg=None, device=0, params=None, init_seed=0, episode_stats=False, **kw):
         self.cfg = cfg or make_config("cartpole")
         self.ctx = Context(self.cfg, device=device, **kw)
         self.model = ActorCritic(self.ctx)
@@ -451,6 +451,21 @@ class Trainer:
         self.steps_per_update = self.ctx.T * self.ctx.N * self.ctx.world
         # main.rs:850-853: the last 100 completed episodes' returns (player 0)
         self.recent_returns = deque(maxlen=100)
+        # episode_stats: every rollout's finished episodes are summarised on the device
+        # (bppo_set_episode_stats); train_update and train_updates feed self.episodes (the
+        # episode/* scalars of main.rs:1134-1217) and the 100-episode windows for every
+        # iteration, the pipelined ones included.  self.recent_returns is then the window's.
+        self.episodes = None
+        if episode_stats:
+            from .episodes import EpisodeWindow, set_episode_stats
+            set_episode_stats(self.ctx, True)
+            self.episodes = EpisodeWindow(self.ctx.seats)
+            self.recent_returns = self.episodes.recent_returns
+
+    def _feed_episodes(self, n):
+        from .episodes import episode_stats
+        for k in range(n):
+            self.episodes.add(*episode_stats(self.ctx, k))
 
     def mean_recent_return(self):
         return float(np.mean(self.recent_returns)) if self.recent_returns else float("nan")
@@ -463,12 +478,15 @@ class Trainer:
         self.vec_env.set_step(self.global_step)
         if track_returns:
             info = collect_rollouts(self.ctx)
-            for ep in rollout_episodes(self.ctx):
-                self.recent_returns.append(ep["total_rewards"][0])
+            if self.episodes is None:                             # (else the window's tail feeds it)
+                for ep in rollout_episodes(self.ctx):
+                    self.recent_returns.append(ep["total_rewards"][0])
             compute_gae(self.ctx)
             metrics = ppo_update(self.ctx, lr, ent)
         else:
             info, metrics = train_step(self.ctx, lr, ent)        # the same three steps, one host wait
+        if self.episodes is not None:
+            self._feed_episodes(1)
         self.global_step += self.steps_per_update                             # main.rs:988
         metrics["episodes"] = info.episodes
         metrics["mean_return"] = info.mean_return
@@ -488,6 +506,8 @@ class Trainer:
         sums = np.zeros(max(len(phase_keys), 1), np.float32)
         self.ctx._chk(L.lib().bppo_train_steps(self.ctx.h, n, lr.ctypes.data, ent.ctypes.data, self.global_step,
                                                 infos, ms, keys, len(phase_keys), sums.ctypes.data))
+        if self.episodes is not None:
+            self._feed_episodes(n)
         out = []
         for k in range(n):
             d = _metrics_dict(ms[k])

@@ -784,11 +784,15 @@ static bppo_status collect_enqueue(bppo_ctx *c, bool summary) {
     else if (!c->wide) BPPO_HIP(c, hipMemcpyAsync(c->d_rew, c->d_rew_raw, TN * 4, hipMemcpyDeviceToDevice, c->stream));
     TRY(tm_end(c, trn));
     int32_t *hv = reinterpret_cast<int32_t *>(roll_host(c, c->coll_slot));     // pinned
-    if (summary) {
+    c->roll_has_stats[c->coll_slot] = c->ep_stats_on != 0;
+    if (summary || c->ep_stats_on) {
         // the summary kernel writes the episode count, the error flags and its partial sums in
-        // the host slot's layout: into d_ep_sum and ONE copy (r05: three)
+        // the host slot's layout: into d_ep_sum and ONE copy (r05: three); the episode
+        // statistics, when on, fill the rest of the slot and ride the same copy
         TRY(launch_episode_summary(c, c->d_ep_sum));
-        BPPO_HIP(c, hipMemcpyAsync(hv, c->d_ep_sum, sizeof(double) * ROLL_HOST_WORDS, hipMemcpyDeviceToHost, c->stream));
+        if (c->ep_stats_on) TRY(launch_episode_stats(c, c->d_ep_sum));
+        const size_t words = c->ep_stats_on ? ROLL_HOST_WORDS : ROLL_BASE_WORDS;
+        BPPO_HIP(c, hipMemcpyAsync(hv, c->d_ep_sum, sizeof(double) * words, hipMemcpyDeviceToHost, c->stream));
     } else {
         BPPO_HIP(c, hipMemcpyAsync(&hv[0], c->d_ep_count, 4, hipMemcpyDeviceToHost, c->stream));
         BPPO_HIP(c, hipMemcpyAsync(&hv[1], c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
@@ -814,6 +818,18 @@ static bppo_status collect_finish(bppo_ctx *c, bppo_rollout_info *info, int slot
     if (hv[1] & 4) { c->err = "opponent pool: pos_to_opp names a model index outside [0, n_models)"; return BPPO_ERR_ARG; }
     if (hv[1] & 8) { c->err = "Invalid action: outside the env's action mask"; return BPPO_ERR_ARG; }   // skull.rs:1116-1128
     if (hv[1]) { c->err = "collect_rollouts: unknown device error flag"; return BPPO_ERR_HIP; }
+    if (c->roll_has_stats[slot]) {
+        // out of the pinned slot (there are two; bppo_train_steps runs n rollouts)
+        const double *sl = roll_host(c, slot);
+        bppo_ctx::EpEntry en;
+        std::memcpy(&en.st, sl + ROLL_STATS_OFF, sizeof en.st);
+        int32_t nt = 0;
+        std::memcpy(&nt, sl + ROLL_NTAIL_OFF, 4);
+        nt = std::max(0, std::min(nt, (int32_t)BPPO_EPISODE_TAIL));
+        en.tail.resize((size_t)nt);
+        if (nt) std::memcpy(en.tail.data(), sl + ROLL_TAIL_OFF, sizeof(bppo_episode_tail) * (size_t)nt);
+        c->ep_entries.push_back(std::move(en));
+    }
     if (info) {
         info->episodes = hv[0];
         info->rng_word_pos = c->rollout_rng_pos[slot];
@@ -830,6 +846,7 @@ static bppo_status collect_finish(bppo_ctx *c, bppo_rollout_info *info, int slot
 
 extern "C" bppo_status bppo_collect_rollouts(bppo_ctx *c, bppo_rollout_info *info) {
     if (!c) return BPPO_ERR_ARG;
+    c->ep_entries.clear();
     // a rollout bppo_train_steps enqueued ahead (it returned an error before using it)
     // IS the next rollout: the RNG and the envs have moved past it already
     if (c->prefetched) c->prefetched = false;
@@ -838,13 +855,13 @@ extern "C" bppo_status bppo_collect_rollouts(bppo_ctx *c, bppo_rollout_info *inf
     return collect_finish(c, info, c->coll_slot);
 }
 
-extern "C" bppo_status bppo_rollout_episodes(bppo_ctx *c, bppo_episode *eps, int32_t cap, int32_t *n) {
-    if (!c) return BPPO_ERR_ARG;
-    int32_t cnt = 0;
-    BPPO_HIP(c, hipMemcpyAsync(&cnt, c->d_ep_count, 4, hipMemcpyDeviceToHost, c->stream));
+// the last rollout's kept episode records in the reference's order; *cnt = the device count
+static bppo_status rollout_records_sorted(bppo_ctx *c, std::vector<EpisodeRec> &recs, int32_t *cnt) {
+    *cnt = 0;
+    BPPO_HIP(c, hipMemcpyAsync(cnt, c->d_ep_count, 4, hipMemcpyDeviceToHost, c->stream));
     BPPO_HIP(c, sync_stream(c));
-    int m = std::min(cnt, c->eps_cap);
-    std::vector<EpisodeRec> recs(m);
+    const int m = std::min(*cnt, c->eps_cap);
+    recs.resize(m);
     if (m) {
         BPPO_HIP(c, hipMemcpyAsync(recs.data(), c->d_eps, sizeof(EpisodeRec) * m, hipMemcpyDeviceToHost, c->stream));
         BPPO_HIP(c, sync_stream(c));
@@ -852,6 +869,61 @@ extern "C" bppo_status bppo_rollout_episodes(bppo_ctx *c, bppo_episode *eps, int
     // reference order: by step, then env index (env.rs:470-483 collects in env order per step)
     std::sort(recs.begin(), recs.end(), [](const EpisodeRec &a, const EpisodeRec &b) {
         return a.step != b.step ? a.step < b.step : a.env_index < b.env_index; });
+    return BPPO_OK;
+}
+
+extern "C" bppo_status bppo_rollout_episode_outcomes(bppo_ctx *c, int32_t *placements, int32_t *has_outcome,
+                                                     int32_t cap, int32_t *n) {
+    if (!c) return BPPO_ERR_ARG;
+    std::vector<EpisodeRec> recs;
+    int32_t cnt = 0;
+    TRY(rollout_records_sorted(c, recs, &cnt));
+    for (int i = 0; i < (int)recs.size() && i < cap; i++) {
+        int32_t pl[BPPO_MAX_PLAYERS];
+        const bool has = opp_unpack_outcome((uint32_t)recs[i].pad, pl);
+        if (placements) std::memcpy(placements + (size_t)i * BPPO_MAX_PLAYERS, pl, sizeof pl);
+        if (has_outcome) has_outcome[i] = has ? 1 : 0;
+    }
+    if (n) *n = cnt;
+    return BPPO_OK;
+}
+
+extern "C" bppo_status bppo_set_episode_stats(bppo_ctx *c, int32_t enable) {
+    if (!c) return BPPO_ERR_ARG;
+    if (enable && ep_key_digits((uint64_t)c->T * (uint64_t)c->N) > EPS_MAX_DIGITS) {
+        c->err = "episode statistics: num_steps * num_envs above 2^33";
+        return BPPO_ERR_UNSUPPORTED;
+    }
+    if (enable) TRY(episode_stats_alloc(c));
+    c->ep_stats_on = enable ? 1 : 0;
+    c->ep_entries.clear();
+    return BPPO_OK;
+}
+
+extern "C" bppo_status bppo_episode_stats_get(bppo_ctx *c, int32_t k, bppo_episode_stats *out, bppo_episode_tail *tail,
+                                              int32_t tail_cap, int32_t *n_tail) {
+    if (!c) return BPPO_ERR_ARG;
+    if (!c->ep_stats_on) { c->err = "episode statistics are off (bppo_set_episode_stats)"; return BPPO_ERR_ARG; }
+    if (c->ep_entries.empty()) { c->err = "episode statistics: no rollout has run since they were switched on"; return BPPO_ERR_ARG; }
+    if (k < 0 || k >= (int32_t)c->ep_entries.size()) {
+        c->err = "episode statistics: rollout " + std::to_string(k) + " of a call that ran " +
+                 std::to_string(c->ep_entries.size());
+        return BPPO_ERR_ARG;
+    }
+    const bppo_ctx::EpEntry &en = c->ep_entries[(size_t)k];
+    if (out) *out = en.st;
+    if (tail)
+        for (int i = 0; i < (int)en.tail.size() && i < tail_cap; i++) tail[i] = en.tail[(size_t)i];
+    if (n_tail) *n_tail = (int32_t)en.tail.size();
+    return BPPO_OK;
+}
+
+extern "C" bppo_status bppo_rollout_episodes(bppo_ctx *c, bppo_episode *eps, int32_t cap, int32_t *n) {
+    if (!c) return BPPO_ERR_ARG;
+    std::vector<EpisodeRec> recs;
+    int32_t cnt = 0;
+    TRY(rollout_records_sorted(c, recs, &cnt));
+    const int m = (int)recs.size();
     for (int i = 0; i < m && i < cap; i++) {
         std::memcpy(eps[i].total_reward, recs[i].total_reward, sizeof(float) * BPPO_MAX_PLAYERS);
         eps[i].length = recs[i].length; eps[i].env_index = recs[i].env_index;
@@ -1293,6 +1365,7 @@ extern "C" bppo_status bppo_train_step(bppo_ctx *c, double lr, double ent_coef, 
     if (!c) return BPPO_ERR_ARG;
     const auto t0 = std::chrono::steady_clock::now();
     c->sync_wait_ms = 0.0;
+    c->ep_entries.clear();
     if (c->prefetched) c->prefetched = false;     // enqueued ahead by bppo_train_steps (see bppo_collect_rollouts)
     else TRY(collect_enqueue(c, info != nullptr));
     TRY(gae_enqueue(c));
@@ -1318,6 +1391,7 @@ extern "C" bppo_status bppo_train_steps(bppo_ctx *c, int32_t n, const double *lr
                                         const char *const *phase_keys, int32_t nkeys, float *phase_sums) {
     if (!c || n < 0 || !lr || !ent_coef || (nkeys > 0 && (!phase_keys || !phase_sums))) return BPPO_ERR_ARG;
     for (int k = 0; k < nkeys; k++) phase_sums[k] = 0.0f;
+    c->ep_entries.clear();
     const uint64_t TN = (uint64_t)c->T * c->N * (uint64_t)c->world;   // the job's env steps per iteration
     for (int32_t k = 0; k < n; k++) {
         const auto t0 = std::chrono::steady_clock::now();

@@ -14,6 +14,7 @@
 #include <memory>
 #include "../../include/bppo.h"
 #include "bppo_device.h"
+#include "bppo_epstats.h"
 
 namespace bppo {
 
@@ -49,7 +50,15 @@ constexpr int EP_SUMMARY_BLOCKS = 128;   // k_ep_summary grid (partial sums per 
 constexpr int WIDE_SPLIT_MIN_ROWS = 32768;   // wide_minibatch: the split-bf16 GEMMs from this minibatch size on
 constexpr int RPOOL_K = 16;              // CfgB rollout: reset states drawn ahead per env (k_reset_pool)
 constexpr int TM_SLOTS = 10;             // phase timer event pairs (enum TM_* below)
-constexpr int ROLL_HOST_WORDS = 2 + 2 * EP_SUMMARY_BLOCKS;     // pinned doubles per rollout slot
+// pinned doubles per rollout slot: [count, err] + k_ep_summary's partials (all a rollout copies
+// while the episode statistics are off), then the rollout's bppo_episode_stats, its tail
+// count and its tail (episode_stats.hip writes them; the one copy then covers the whole slot)
+constexpr int ROLL_BASE_WORDS = 2 + 2 * EP_SUMMARY_BLOCKS;
+constexpr int ROLL_STATS_OFF = ROLL_BASE_WORDS;
+constexpr int ROLL_NTAIL_OFF = ROLL_STATS_OFF + (int)(sizeof(bppo_episode_stats) / 8);
+constexpr int ROLL_TAIL_OFF = ROLL_NTAIL_OFF + 1;
+constexpr int ROLL_HOST_WORDS = ROLL_TAIL_OFF + BPPO_EPISODE_TAIL * (int)(sizeof(bppo_episode_tail) / 8);
+static_assert(sizeof(bppo_episode_stats) % 8 == 0 && sizeof(bppo_episode_tail) % 8 == 0, "slot layout in doubles");
 constexpr int ADV_STREAM_BLOCKS = 512, ADV_STREAM_MAXM = 16;   // k_adv_stream grid, most minibatches
 // metric slots after the gradient, d_grad[np + k]: GRAD_METRIC_SLOTS (= WM_COUNT, bppo_wide.h)
 // travel with the gradient through the W > 1 SUM all-reduce; value_error_max (slot
@@ -363,7 +372,16 @@ struct bppo_ctx {
     bppo::EpisodeRec *d_eps = nullptr;
     int32_t *d_ep_count = nullptr;
     int32_t eps_cap = 0;
-    double *d_ep_sum = nullptr;          // [EP_SUMMARY_BLOCKS][2] partial sums (return, length)
+    double *d_ep_sum = nullptr;          // [ROLL_HOST_WORDS] one host slot's layout
+    // episode statistics (episode_stats.hip, bppo_set_episode_stats): scratch allocated when
+    // first switched on; one entry per rollout of the current hot-path call
+    int ep_stats_on = 0;
+    bppo_episode_stats *d_ep_part = nullptr;   // [EPS_BLOCKS] per-block partials
+    int32_t *d_ep_sel = nullptr;               // [EPS_SEL_WORDS] digit histograms + the compaction counter
+    bppo::EpisodeRec *d_ep_cand = nullptr;     // [BPPO_EPISODE_TAIL] the tail's records, unordered
+    bool roll_has_stats[2] = {false, false};   // the rollout in pinned slot s was enqueued with them on
+    struct EpEntry { bppo_episode_stats st; std::vector<bppo_episode_tail> tail; };
+    std::vector<EpEntry> ep_entries;
     int32_t *d_err = nullptr;
     // main RNG
     bppo::Key8 rng_key{};
@@ -537,6 +555,9 @@ bppo_status launch_cartpole_vecenv_step(bppo_ctx *c, const int32_t *d_actions, f
 bppo_status launch_cartpole_observe(bppo_ctx *c, float *d_obs_out);
 bppo_status launch_obs_norm_merge(bppo_ctx *c);
 bppo_status launch_episode_summary(bppo_ctx *c, double *host_slot);
+// (episode_stats.hip) the rollout's statistics and tail into the slot layout at d_slot
+bppo_status episode_stats_alloc(bppo_ctx *c);
+bppo_status launch_episode_stats(bppo_ctx *c, double *d_slot);
 bppo_status launch_obs_norm_rows(bppo_ctx *c, int rows, float *x, int ld, float *raw);
 bppo_status launch_obs_norm_rows_on(bppo_ctx *c, int rows, float *x, int ld, float *raw, const double *on);
 bppo_status launch_bootstrap(bppo_ctx *c, const double *mean, const double *sd, int norm_on);

@@ -54,6 +54,12 @@ __host__ __device__ inline uint32_t opp_pack_outcome(bool has, const int32_t pla
     for (int p = 0; p < 6; p++) v |= ((uint32_t)placement[p] & 15u) << (4 * p);
     return v;
 }
+// -> whether the env reported an outcome; the placements are 0 where it did not
+__host__ __device__ inline bool opp_unpack_outcome(uint32_t w, int32_t placement[6]) {
+    const bool has = (w >> 24) & 1u;
+    for (int p = 0; p < 6; p++) placement[p] = has ? (int32_t)((w >> (4 * p)) & 15u) : 0;
+    return has;
+}
 
 struct SampleArgs {
     int N, P;

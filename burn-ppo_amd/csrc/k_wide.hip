@@ -246,7 +246,12 @@ __global__ void k_wide_step(WideStepArgs a) {
         if (slot < a.eps_cap) {
             EpisodeRec rec;
             for (int p = 0; p < BPPO_MAX_PLAYERS; p++) rec.total_reward[p] = p < E::P ? er[p] : 0.0f;
-            rec.length = len; rec.env_index = e; rec.step = a.t; rec.pad = 0;
+            rec.length = len; rec.env_index = e; rec.step = a.t;
+            // game_outcome before the reset (env.rs:442-450), for the episode statistics and
+            // bppo_rollout_episode_outcomes; CartPole has none: 0
+            int32_t pl[6];
+            const bool has = E::outcome(s, pl);
+            rec.pad = (int32_t)opp_pack_outcome(has, pl);
             a.eps[slot] = rec;
         }
         for (int p = 0; p < E::P; p++) er[p] = 0.0f;

@@ -105,6 +105,42 @@ typedef struct {
     uint64_t rng_word_pos;       /* main RNG position after the rollout */
 } bppo_rollout_info;
 
+/* The finished episodes of one rollout as mergeable statistics: what the reference's
+ * "episode/..." scalars (main.rs:1134-1217) and compute_avg_points (env.rs:208-261) need, so a log
+ * interval's scalars are the merge of its rollouts' blocks (add the sums and counts, take the
+ * min of the minima and the max of the maxima).  Computed on the device from the rollout's
+ * episode records (bppo_set_episode_stats).  P below = the seated player count (Skull:
+ * player_count; CartPole: 1); slots >= P keep the identities.
+ * Every field but return_sum is exact and independent of the order of the records.
+ * return_sum is an f64 sum in the order of the device's record slots: exact whenever the
+ * returns are integers (Connect Four, CartPole, the unshaped games); with shaped rewards its
+ * last bits may differ from run to run, because the slots are handed out by atomics (within
+ * n 2^-53 sum|x| of the exact sum, as any f64 sum of n terms).
+ * No finished episode: the merge identities (length_min INT32_MAX, length_max 0, return_min
+ * +inf, return_max -inf, sums 0). */
+typedef struct {
+    int32_t episodes;            /* finished this rollout (the device count) */
+    int32_t kept;                /* of those, records kept and counted below: min(episodes, T N + 4096) */
+    int32_t length_min, length_max;
+    int64_t length_sum;
+    int32_t with_outcome;        /* records whose env reported a game_outcome */
+    int32_t draws;               /* of those: every seated placement is 1 */
+    double return_sum[BPPO_MAX_PLAYERS];
+    float return_min[BPPO_MAX_PLAYERS], return_max[BPPO_MAX_PLAYERS];
+    int32_t outcome_games[BPPO_MAX_PLAYERS];   /* outcomes seat p took part in */
+    /* twice the Swiss points of seat p: a game of n seats adds 2 n - 2 place - (tied - 1),
+     * tied = the seats sharing place (env.rs:236-242 doubled: an exact integer) */
+    int64_t points2_sum[BPPO_MAX_PLAYERS];
+} bppo_episode_stats;
+
+/* one episode of the last-100 window (main.rs:842-875) */
+#define BPPO_EPISODE_TAIL 100
+typedef struct {
+    float total_reward[BPPO_MAX_PLAYERS];
+    int32_t placement[BPPO_MAX_PLAYERS];    /* 1 = first; 0 beyond the seated players and without an outcome */
+    int32_t length, env_index, step, has_outcome;
+} bppo_episode_tail;
+
 /* UpdateMetrics, ppo.rs:1342-1369 */
 typedef struct {
     float policy_loss, value_loss, entropy, entropy_scaled, approx_kl, clip_fraction;
@@ -229,6 +265,31 @@ bppo_status bppo_popart_set(bppo_ctx *ctx, const double *state4);
 /* ---- the hot path ------------------------------------------------------- */
 bppo_status bppo_collect_rollouts(bppo_ctx *ctx, bppo_rollout_info *info);
 bppo_status bppo_rollout_episodes(bppo_ctx *ctx, bppo_episode *eps, int32_t cap, int32_t *n);
+/* the same episodes' game_outcome (env.rs:442-450, read before the auto-reset), in
+ * bppo_rollout_episodes' order: placements [cap][6] per seat (1 = first; 0 beyond the seated
+ * players and where the env reported no outcome: always for CartPole), has_outcome [cap];
+ * either may be NULL; *n = the rollout's episode count.  Works with the statistics below on
+ * or off. */
+bppo_status bppo_rollout_episode_outcomes(bppo_ctx *ctx, int32_t *placements, int32_t *has_outcome, int32_t cap,
+                                          int32_t *n);
+/* Episode statistics on the device (off by default): enable != 0 makes every rollout from
+ * now on, those bppo_train_steps pipelines included, leave its bppo_episode_stats and its
+ * last BPPO_EPISODE_TAIL episodes beside its bppo_rollout_info: up to five small kernels over
+ * the episode records and a larger copy of the same pinned slot; no record crosses PCIe.
+ * Off, nothing is launched or copied that is not without this call. */
+bppo_status bppo_set_episode_stats(bppo_ctx *ctx, int32_t enable);
+/* rollout k of the last hot-path call: 0 for bppo_collect_rollouts / bppo_train_step, 0..n-1
+ * for bppo_train_steps.  A rollout bppo_train_steps ran ahead and an error left pending is
+ * not part of the failed call: it is entry 0 of the call that consumes it.  tail receives the
+ * first min(tail_cap, *n_tail) of the rollout's last min(100, kept) episodes, oldest first in
+ * the reference's push order (step, then env index): pushed in that order into 100-deep
+ * deques they leave what main.rs:842-875 keeps.  out, tail, n_tail may be NULL.
+ * BPPO_ERR_ARG with a message: the statistics are off, k is out of range, or no rollout has
+ * run since they were switched on.  Reads host memory only: no HIP call. */
+bppo_status bppo_episode_stats_get(bppo_ctx *ctx, int32_t k, bppo_episode_stats *out, bppo_episode_tail *tail,
+                                   int32_t tail_cap, int32_t *n_tail);
+size_t bppo_episode_stats_size(void);
+size_t bppo_episode_tail_size(void);
 bppo_status bppo_compute_gae(bppo_ctx *ctx);
 bppo_status bppo_ppo_update(bppo_ctx *ctx, double lr, double ent_coef, bppo_update_metrics *m);
 /* the three calls above as one (main.rs:860-947 then ppo.rs:1661-2112): enqueued back to
@@ -622,6 +683,17 @@ bppo_status bppo_debug_sample(int32_t A, int32_t B, const float *logits, const u
 bppo_status bppo_debug_eval_sample(int32_t device, int32_t A, int32_t B, const float *logits, const uint8_t *masks,
                                    const float *temps, uint64_t seed, uint64_t stream, uint64_t word_pos,
                                    int32_t *actions, int32_t *draws_used);
+/* episode statistics parity hook (host buffers, no context): the statistics and the tail of n
+ * episode records as a rollout of T steps of N envs with P seated players would report them.
+ * outcome_words [n] (NULL = no outcomes): placement of seat p in bits [4p, 4p + 4), bit 24 =
+ * the env reported an outcome.  device = 0 runs the host build of the same source (a loop and
+ * a sort), 1 the kernels on an uploaded copy.  tail [100], *n_tail = min(100, n).
+ * BPPO_ERR_ARG before any HIP call: n < 0, P outside 1..6, T or N < 1, a NULL eps with n > 0,
+ * a NULL out / tail / n_tail, a record whose step is outside [0, T) or env_index outside
+ * [0, N), or two records with one (step, env_index). */
+bppo_status bppo_debug_episode_stats(int32_t device, int32_t n, const bppo_episode *eps, const int32_t *outcome_words,
+                                     int32_t P, int32_t N, int32_t T, bppo_episode_stats *out,
+                                     bppo_episode_tail *tail, int32_t *n_tail);
 /* generate_permutations (eval.rs:1591-1612): out [n!][n], n in 1..6 */
 bppo_status bppo_debug_eval_perms(int32_t n, int32_t *out);
 
