@@ -118,6 +118,15 @@ class UpdateMetrics(C.Structure):
         [(n, C.c_float) for n in POPART_METRICS]
 
 
+class FoldArgs(C.Structure):
+    """bppo_debug_fold_args: what the update's metric fold reads besides the minibatch rows"""
+    _fields_ = [("value_coef", C.c_float), ("ent_coef", C.c_float), ("A", C.c_int32), ("env_kind", C.c_int32),
+                ("B", C.c_uint64), ("ev4", C.c_double * 4), ("ev_mode", C.c_int32), ("ev_ref", C.c_float),
+                ("epochs_run", C.c_int32), ("normalize_values", C.c_int32),
+                ("pa_tsum", C.c_double), ("pa_tsq", C.c_double), ("pa_tcount", C.c_double),
+                ("pa_rescale_mag", C.c_float)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
 
 # every symbol declared in include/bppo.h (tests check the .so exports them all)
@@ -130,7 +139,7 @@ EXPORTS = (
     "bppo_set_allreduce", "bppo_set_allreduce_async", "bppo_get_stream", "bppo_opponents_set", "bppo_opponents_get_envs", "bppo_buffer_get", "bppo_buffer_set", "bppo_gae_device", "bppo_gae_rows_device",
     "bppo_gae_mp_device", "bppo_last_kernel_ms", "bppo_debug_libm", "bppo_debug_shuffle_chain", "bppo_debug_chain_walk2", "bppo_minibatch_rows",
     "bppo_debug_fisher_yates", "bppo_debug_gemm", "bppo_debug_return_norm", "bppo_debug_shuffle_engine", "bppo_debug_sample",
-    "bppo_debug_device_memory",
+    "bppo_debug_device_memory", "bppo_debug_fold_metrics",
     "bppo_rng_fill_bytes", "bppo_rng_from_seed", "bppo_rng_key_get", "bppo_num_param_tensors",
     "bppo_optimizer_get", "bppo_optimizer_set", "bppo_popart_get", "bppo_popart_set",
     "bppo_config_size", "bppo_update_metrics_size", "bppo_episode_size", "bppo_rollout_info_size",
@@ -233,6 +242,7 @@ def lib():
         "bppo_debug_shuffle_engine": (i32, [u64, u64, u64, C.c_uint32, i32, u64, i32, i32, vp, vp, vp]),
         "bppo_debug_sample": (i32, [i32, i32, vp, vp, u64, u64, u64, vp, vp]),
         "bppo_debug_device_memory": (i32, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "bppo_debug_fold_metrics": (i32, [vp, i32, C.POINTER(FoldArgs), C.POINTER(UpdateMetrics)]),
         "bppo_rng_fill_bytes": (i32, [vp, vp, sz]),
         "bppo_rng_from_seed": (i32, [vp, vp]),
         "bppo_rng_key_get": (i32, [vp, vp]),

@@ -1,8 +1,7 @@
-// bppo_api.hip — the C-ABI (include/bppo.h): context lifecycle, the
-// host-side orchestration of one update (collect_rollouts -> bootstrap + GAE ->
-// ppo_update, main.rs:724-963), the rand-0.8 shuffle chain thread, parity hooks.
+// bppo_api.hip — the C-ABI (include/bppo.h): context lifecycle, state getters and
+// setters, buffer access, parity hooks.  The training loop (collect_rollouts ->
+// bootstrap + GAE -> ppo_update, bppo_train_step(s)) is train_loop.hip.
 #include <algorithm>
-#include <pthread.h>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -11,28 +10,14 @@
 #include <new>
 #include <thread>
 #include <sys/prctl.h>
-#include <x86intrin.h>
 #include "bppo_internal.h"
 #include "shuffle_host.h"
 #include "bppo_wide.h"
+#include "bppo_update_metrics.h"
 
 using namespace bppo;
 
 namespace bppo {
-// TSC ticks per millisecond, measured once against steady_clock (shuffle engine
-// diagnostics)
-static double tsc_per_ms() {
-    static double v = 0.0;
-    if (v == 0.0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        const uint64_t c0 = __rdtsc();
-        std::this_thread::sleep_for(std::chrono::milliseconds(20));
-        const uint64_t c1 = __rdtsc();
-        v = (double)(c1 - c0) / std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return v;
-}
-
 
 NetLayout make_layout(const bppo_config &c, int obs_dim, int priv_dim, int act_dim) {
     NetLayout L;
@@ -126,18 +111,6 @@ bppo_status launch_libm(int which, const float *d_x, float *d_y, size_t n) {
 }  // namespace bppo
 
 // ======================================================================= ABI
-static float powi_f32(float a, int b) {   // compiler-rt __powisf2 (Rust f32::powi)
-    int recip = b < 0;
-    float r = 1.0f;
-    for (;;) {
-        if (b & 1) r *= a;
-        b /= 2;
-        if (b == 0) break;
-        a *= a;
-    }
-    return recip ? 1.0f / r : r;
-}
-
 extern "C" size_t bppo_config_size(void) { return sizeof(bppo_config); }
 extern "C" size_t bppo_update_metrics_size(void) { return sizeof(bppo_update_metrics); }
 extern "C" size_t bppo_episode_size(void) { return sizeof(bppo_episode); }
@@ -151,26 +124,7 @@ extern "C" const char *bppo_last_error(const bppo_ctx *c) { return c ? c->err.c_
 // instead of polling (polling eats the CPU quota the shuffle walkers run on)
 // (hipEventSynchronize on a blocking-sync event still spun here: measured ~1 CPU per
 // process for the whole update; a sleeping poll at 20 us with 1 us timer slack frees it)
-// The per-update wait of bppo_train_steps (~12 ms on CfgB) repeats from one update to
-// the next, so it starts with ONE coarse sleep of 70 % of the recent waits and only
-// then polls at 20 us: every poll is a wake-up plus an event query, and polling the
-// whole wait cost the driving thread ~1 CPU per rank (14 ms of CPU per 13.9 ms update
-// in r03h), CPU the shuffle walkers of an 8-rank node need.
-static hipError_t wait_event(bppo_ctx *c, hipEvent_t ev) {   // sleeping poll (see sync_stream)
-    const auto t0 = std::chrono::steady_clock::now();
-    hipError_t e = event_query(ev);
-    if (e == hipErrorNotReady) {
-        if (c->wait_est_us > 200.0)
-            std::this_thread::sleep_for(std::chrono::microseconds((long)(0.7 * c->wait_est_us)));
-        while ((e = event_query(ev)) == hipErrorNotReady) std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->wait_est_us = c->wait_est_us > 0.0 ? 0.5 * c->wait_est_us + 500.0 * ms : 1000.0 * ms;
-    c->sync_wait_ms += ms;
-    return e;
-}
-
-static hipError_t sync_stream(bppo_ctx *c) {
+hipError_t sync_stream(bppo_ctx *c) {   // (also train_loop.hip)
     const auto t0 = std::chrono::steady_clock::now();
     hipError_t e;
     if (!c->ev_block) e = hipStreamSynchronize(c->stream);
@@ -691,187 +645,6 @@ extern "C" bppo_status bppo_popart_set(bppo_ctx *c, const double *st) {
     return BPPO_OK;
 }
 
-static bppo_status tm_begin(bppo_ctx *c, int slot) {
-    BPPO_HIP(c, hipEventRecord(c->ev[slot][0], c->stream));
-    return BPPO_OK;
-}
-static bppo_status tm_end(bppo_ctx *c, int slot) {
-    BPPO_HIP(c, hipEventRecord(c->ev[slot][1], c->stream));
-    return BPPO_OK;
-}
-static void tm_read(bppo_ctx *c, int slot) {
-    float ms = 0;
-    if (event_ms(c->ev[slot][0], c->ev[slot][1], &ms)) c->last_ms[slot] = ms;
-}
-
-// Fisher-Yates of every epoch of the engine's job in `slot` whose J is already on
-// the device (the host engine has resolved it), in epoch order on fy_stream,
-// each into its own permutation buffer (ppo.rs:1816 indices.shuffle; the
-// permutation of epoch e depends only on that epoch's RNG words)
-static bppo_status fy_enqueue_ready(bppo_ctx *c, int slot) {
-    const size_t B = (size_t)c->T * c->N;
-    if (slot != c->fy_slot) {
-        // a new update's permutations overwrite perm/inv, which the previous update's
-        // minibatches may still be reading when its successor's rollout is enqueued
-        // behind it (bppo_train_steps): wait for the end of that update
-        c->fy_slot = slot; c->fy_done = 0;
-        BPPO_HIP(c, hipStreamWaitEvent(c->fy_stream, c->ev_upd, 0));
-    }
-    if (c->shuf.failed(c->err)) return BPPO_ERR_HIP;
-    while (c->fy_done < c->cfg.num_epochs && c->shuf.epoch_ready(slot, c->fy_done)) {
-        const int e = c->fy_done;
-        // the engine thread may have recorded a HIP failure (J upload, expansion, event) and
-        // then marked this epoch ready: its J is not to be permuted
-        if (c->shuf.failed(c->err)) return BPPO_ERR_HIP;
-        BPPO_HIP(c, hipStreamWaitEvent(c->fy_stream, c->shuf.ev[slot][e], 0));
-        if (e > 0) BPPO_HIP(c, hipStreamWaitEvent(c->fy_stream, c->fy_ev[e - 1], 0));   // shared scratch
-        BPPO_HIP(c, hipEventRecord(c->ev[TM_SHUFFLE][0], c->fy_stream));
-        BPPO_HIP(c, fisher_yates_device(c->shuf.d_J[slot] + (size_t)e * B, (uint32_t)B, c->d_fy, c->d_scan,
-                                        c->d_perm_ep + (size_t)e * B, c->fy_stream, &c->fyr,
-                                        c->d_inv_ep + (size_t)e * B));
-        BPPO_HIP(c, hipEventRecord(c->ev[TM_SHUFFLE][1], c->fy_stream));
-        BPPO_HIP(c, hipEventRecord(c->fy_ev[e], c->fy_stream));
-        c->fy_done++;
-    }
-    return BPPO_OK;
-}
-
-// collect_rollouts (ppo.rs:213-500), enqueue half: everything up to the episode
-// summary and the device flags' copies into pinned host words (no host wait)
-// the rollout's device flags and episode partials land in one of two pinned slots, so
-// a rollout enqueued behind an update (bppo_train_steps) does not overwrite the
-// previous rollout's before they are read
-static double *roll_host(bppo_ctx *c, int slot) { return c->h_red + 4 * 1024 + 64 + (size_t)slot * ROLL_HOST_WORDS; }
-
-static bppo_status collect_enqueue(bppo_ctx *c, bool summary) {
-    const size_t TN = (size_t)c->T * c->N;
-    c->coll_slot ^= 1;
-    const int tro = c->coll_slot ? TM_ROLLOUT_B : TM_ROLLOUT, trn = c->coll_slot ? TM_RETNORM_B : TM_RETNORM;
-    // the episode counter and error flags start at 0: zeroed here for the wide envs, by the
-    // CartPole launcher (in its Gumbel kernel where that runs on the update stream)
-    if (c->wide) {
-        BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
-        BPPO_HIP(c, hipMemsetAsync(c->d_err, 0, 4, c->stream));
-        if (opp_active(c)) TRY(opp_records_clear(c));   // the finished opponent games go with the episodes
-    }
-    const uint64_t base = c->rng_pos;
-    TRY(tm_begin(c, tro));
-    if (c->wide) TRY(wide_collect(c, base));
-    else {
-        TRY(launch_cartpole_rollout(c, base, nullptr, nullptr, c->cfg.normalize_obs));
-        TRY(popart_denorm(c, c->d_val, TN));            // ppo.rs:355-359 (multi-player: in the sampler)
-    }
-    TRY(tm_end(c, tro));
-    // self-play: the update's shuffles start right after this rollout's Gumbel words,
-    // so the epochs the engine has resolved are permuted now, beside the rollout
-    // (beside the rollout is where they cost least: it leaves VGPRs and LDS free on every
-    // CU, while the minibatch kernels fill them -- profiles/r03j_mb_overlap.txt)
-    if (!opp_active(c)) {
-        c->shuf_slot = c->shuf.ensure(base + TN * (uint64_t)c->A);
-        TRY(fy_enqueue_ready(c, c->shuf_slot));
-    }
-    if (opp_active(c)) {
-        // opponent pool: seat reshuffles drew a data-dependent number of words
-        TRY(opp_rollout_end(c));
-    } else {
-        c->rng_pos = base + TN * (uint64_t)c->A;   // one word per (env, action) per step
-        // this update's shuffles start here; the engine usually began them already
-        c->shuf_slot = c->shuf.ensure(c->rng_pos);
-    }
-    if (c->cfg.normalize_obs) TRY(launch_obs_norm_merge(c));       // ppo.rs:495-497
-    TRY(tm_begin(c, trn));
-    if (c->cfg.normalize_returns) TRY(launch_return_norm(c));      // ppo.rs:390-408
-    else if (!c->wide) BPPO_HIP(c, hipMemcpyAsync(c->d_rew, c->d_rew_raw, TN * 4, hipMemcpyDeviceToDevice, c->stream));
-    TRY(tm_end(c, trn));
-    int32_t *hv = reinterpret_cast<int32_t *>(roll_host(c, c->coll_slot));     // pinned
-    c->roll_has_stats[c->coll_slot] = c->ep_stats_on != 0;
-    if (summary || c->ep_stats_on) {
-        // the summary kernel writes the episode count, the error flags and its partial sums in
-        // the host slot's layout: into d_ep_sum and ONE copy (r05: three); the episode
-        // statistics, when on, fill the rest of the slot and ride the same copy
-        TRY(launch_episode_summary(c, c->d_ep_sum));
-        if (c->ep_stats_on) TRY(launch_episode_stats(c, c->d_ep_sum));
-        const size_t words = c->ep_stats_on ? ROLL_HOST_WORDS : ROLL_BASE_WORDS;
-        BPPO_HIP(c, hipMemcpyAsync(hv, c->d_ep_sum, sizeof(double) * words, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        BPPO_HIP(c, hipMemcpyAsync(&hv[0], c->d_ep_count, 4, hipMemcpyDeviceToHost, c->stream));
-        BPPO_HIP(c, hipMemcpyAsync(&hv[1], c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    c->collected = 1; c->gae_done = 0;
-    c->rollout_rng_pos[c->coll_slot] = c->rng_pos;   // RNG position after the rollout (info; the update moves it on)
-    return BPPO_OK;
-}
-
-// finish half, after the stream has drained past collect_enqueue: device error
-// flags -> status, episode summary -> info
-static bppo_status collect_finish(bppo_ctx *c, bppo_rollout_info *info, int slot) {
-    float ms = 0;
-    const int tro = slot ? TM_ROLLOUT_B : TM_ROLLOUT, trn = slot ? TM_RETNORM_B : TM_RETNORM;
-    if (event_ms(c->ev[tro][0], c->ev[tro][1], &ms)) c->last_ms[TM_ROLLOUT] = ms;
-    if (event_ms(c->ev[trn][0], c->ev[trn][1], &ms)) c->last_ms[TM_RETNORM] = ms;
-    const int32_t *hv = reinterpret_cast<const int32_t *>(roll_host(c, slot));
-    const double *part = roll_host(c, slot) + 2;
-    // device error bits: 1 non-finite log-prob, 2 empty action mask, 4 opponent seat
-    // table names a model outside [0, n_models)
-    if (hv[1] & 2) { c->err = "Empty action mask: an env has no valid action"; return BPPO_ERR_EMPTY_MASK; }
-    if (hv[1] & 1) { c->err = "NaN/Inf in log probs — model producing corrupt logits"; return BPPO_ERR_NONFINITE; }
-    if (hv[1] & 4) { c->err = "opponent pool: pos_to_opp names a model index outside [0, n_models)"; return BPPO_ERR_ARG; }
-    if (hv[1] & 8) { c->err = "Invalid action: outside the env's action mask"; return BPPO_ERR_ARG; }   // skull.rs:1116-1128
-    if (hv[1]) { c->err = "collect_rollouts: unknown device error flag"; return BPPO_ERR_HIP; }
-    if (c->roll_has_stats[slot]) {
-        // out of the pinned slot (there are two; bppo_train_steps runs n rollouts)
-        const double *sl = roll_host(c, slot);
-        bppo_ctx::EpEntry en;
-        std::memcpy(&en.st, sl + ROLL_STATS_OFF, sizeof en.st);
-        int32_t nt = 0;
-        std::memcpy(&nt, sl + ROLL_NTAIL_OFF, 4);
-        nt = std::max(0, std::min(nt, (int32_t)BPPO_EPISODE_TAIL));
-        en.tail.resize((size_t)nt);
-        if (nt) std::memcpy(en.tail.data(), sl + ROLL_TAIL_OFF, sizeof(bppo_episode_tail) * (size_t)nt);
-        c->ep_entries.push_back(std::move(en));
-    }
-    if (info) {
-        info->episodes = hv[0];
-        info->rng_word_pos = c->rollout_rng_pos[slot];
-        info->mean_return = 0; info->mean_length = 0;
-        const int n = std::min(hv[0], c->eps_cap);
-        if (n > 0) {
-            double sr = 0, sl = 0;
-            for (int b = 0; b < EP_SUMMARY_BLOCKS; b++) { sr += part[2 * b]; sl += part[2 * b + 1]; }
-            info->mean_return = (float)(sr / n); info->mean_length = (float)(sl / n);
-        }
-    }
-    return BPPO_OK;
-}
-
-extern "C" bppo_status bppo_collect_rollouts(bppo_ctx *c, bppo_rollout_info *info) {
-    if (!c) return BPPO_ERR_ARG;
-    c->ep_entries.clear();
-    // a rollout bppo_train_steps enqueued ahead (it returned an error before using it)
-    // IS the next rollout: the RNG and the envs have moved past it already
-    if (c->prefetched) c->prefetched = false;
-    else TRY(collect_enqueue(c, info != nullptr));
-    BPPO_HIP(c, sync_stream(c));
-    return collect_finish(c, info, c->coll_slot);
-}
-
-// the last rollout's kept episode records in the reference's order; *cnt = the device count
-static bppo_status rollout_records_sorted(bppo_ctx *c, std::vector<EpisodeRec> &recs, int32_t *cnt) {
-    *cnt = 0;
-    BPPO_HIP(c, hipMemcpyAsync(cnt, c->d_ep_count, 4, hipMemcpyDeviceToHost, c->stream));
-    BPPO_HIP(c, sync_stream(c));
-    const int m = std::min(*cnt, c->eps_cap);
-    recs.resize(m);
-    if (m) {
-        BPPO_HIP(c, hipMemcpyAsync(recs.data(), c->d_eps, sizeof(EpisodeRec) * m, hipMemcpyDeviceToHost, c->stream));
-        BPPO_HIP(c, sync_stream(c));
-    }
-    // reference order: by step, then env index (env.rs:470-483 collects in env order per step)
-    std::sort(recs.begin(), recs.end(), [](const EpisodeRec &a, const EpisodeRec &b) {
-        return a.step != b.step ? a.step < b.step : a.env_index < b.env_index; });
-    return BPPO_OK;
-}
-
 extern "C" bppo_status bppo_rollout_episode_outcomes(bppo_ctx *c, int32_t *placements, int32_t *has_outcome,
                                                      int32_t cap, int32_t *n) {
     if (!c) return BPPO_ERR_ARG;
@@ -933,73 +706,6 @@ extern "C" bppo_status bppo_rollout_episodes(bppo_ctx *c, bppo_episode *eps, int
     return BPPO_OK;
 }
 
-// bootstrap + GAE (main.rs:877-947)
-// enqueue half (the CartPole path has no host read in it)
-static bppo_status gae_enqueue(bppo_ctx *c) {
-    c->prefetched = false;        // a pending rollout is consumed here (e.g. after a bppo_train_steps error)
-    if (c->wide) {
-        TRY(tm_begin(c, TM_GAE));
-        TRY(wide_bootstrap_gae(c));
-        TRY(tm_end(c, TM_GAE));
-        c->gae_done = 1;
-        return BPPO_OK;
-    }
-    TRY(tm_begin(c, TM_BOOT));
-    TRY(launch_bootstrap(c, nullptr, nullptr, c->cfg.normalize_obs));
-    TRY(popart_denorm(c, c->d_last_v, (size_t)c->N));   // main.rs:898-907
-    TRY(tm_end(c, TM_BOOT));
-    TRY(tm_begin(c, TM_GAE));
-    bool packed = false;
-    hipError_t he = hipSuccess;
-    bppo_status s = launch_gae_1p(c->d_rew, c->d_done, c->d_val, c->d_last_v, c->T, c->N,
-                                  (float)c->cfg.gamma, (float)c->cfg.gae_lambda, c->d_adv, c->d_ret,
-                                  c->stream, c->rows_from_rollout ? c->d_rowB : nullptr, &packed, &he);
-    c->rows_packed = packed;
-    if (s != BPPO_OK) return he != hipSuccess ? hip_fail(c, he, "k_gae_1p launch") : s;
-    TRY(tm_end(c, TM_GAE));
-    c->gae_done = 1;
-    return BPPO_OK;
-}
-
-extern "C" bppo_status bppo_compute_gae(bppo_ctx *c) {
-    if (!c || !c->collected) { if (c) c->err = "compute_gae before collect_rollouts"; return BPPO_ERR_ARG; }
-    TRY(gae_enqueue(c));
-    BPPO_HIP(c, sync_stream(c));
-    if (!c->wide) tm_read(c, TM_BOOT);
-    tm_read(c, TM_GAE);
-    return BPPO_OK;
-}
-
-// ppo.rs:1268-1294 compute_explained_variance as the reference computes it: f32
-// iterator sums in order (each chain sequential; the two independent chains of a
-// round are interleaved only for instruction-level parallelism), population
-// variances, no fma contraction ((r - mean).powi(2) is a multiply, then the add)
-static float ev_reference_f32(const float *v, const float *r, const float *valid, size_t n_all) {
-#pragma clang fp contract(off)
-    size_t n_ = 0;
-    float s_r = 0.0f, s_res = 0.0f;
-    for (size_t i = 0; i < n_all; i++) {
-        if (valid && !(valid[i] > 0.5f)) continue;     // opponent pool: learner rows (ppo.rs:2047-2056)
-        s_r += r[i];
-        s_res += r[i] - v[i];
-        n_++;
-    }
-    const float n = (float)n_;
-    if (n < 2.0f) return 0.0f;
-    const float mr = s_r / n, mres = s_res / n;
-    float q_r = 0.0f, q_res = 0.0f;
-    for (size_t i = 0; i < n_all; i++) {
-        if (valid && !(valid[i] > 0.5f)) continue;
-        const float d = r[i] - mr;
-        q_r += d * d;
-        const float e = (r[i] - v[i]) - mres;
-        q_res += e * e;
-    }
-    const float vr = q_r / n;
-    if (vr < 1e-8f) return 0.0f;
-    return 1.0f - (q_res / n) / vr;
-}
-
 extern "C" bppo_status bppo_set_explained_variance_mode(bppo_ctx *c, int32_t mode) {
     if (!c || mode < 0 || mode > 1) return BPPO_ERR_ARG;
     if (mode == 1 && !c->h_ev_v) {
@@ -1039,388 +745,6 @@ extern "C" bppo_status bppo_debug_record_params(bppo_ctx *c, float *host, int32_
 extern "C" bppo_status bppo_set_minibatch_kernel(bppo_ctx *c, int32_t mode) {
     if (!c || mode < 0 || mode > 2) return BPPO_ERR_ARG;
     c->mb_kernel = mode;
-    return BPPO_OK;
-}
-
-// mode 1: copy the buffers the metric reads (stream order: after GAE, before anything
-// later rewrites them) and sum them on a host thread while the update runs
-static bppo_status ev_reference_begin(bppo_ctx *c, const float *d_valid) {
-    const size_t TN = (size_t)c->T * c->N;
-    // a thread left by an update that returned early still reads the pinned buffers
-    // (or waits on ev_copied): it ends before they are refilled or the event re-recorded
-    if (c->ev_thread.joinable()) c->ev_thread.join();
-    BPPO_HIP(c, hipEventRecord(c->ev_gae, c->stream));
-    BPPO_HIP(c, hipStreamWaitEvent(c->ev_stream, c->ev_gae, 0));
-    BPPO_HIP(c, hipMemcpyAsync(c->h_ev_v, c->d_val, TN * 4, hipMemcpyDeviceToHost, c->ev_stream));
-    BPPO_HIP(c, hipMemcpyAsync(c->h_ev_r, c->d_ret, TN * 4, hipMemcpyDeviceToHost, c->ev_stream));
-    if (d_valid) BPPO_HIP(c, hipMemcpyAsync(c->h_ev_valid, d_valid, TN * 4, hipMemcpyDeviceToHost, c->ev_stream));
-    BPPO_HIP(c, hipEventRecord(c->ev_copied, c->ev_stream));
-    const bool vf = d_valid != nullptr;
-    c->ev_thread = std::thread([c, TN, vf]() {
-        (void)pthread_setname_np(pthread_self(), "bppo-ev");
-        (void)hipEventSynchronize(c->ev_copied);
-        c->ev_ref = ev_reference_f32(c->h_ev_v, c->h_ev_r, vf ? c->h_ev_valid : nullptr, TN);
-    });
-    return BPPO_OK;
-}
-
-// ppo_update (ppo.rs:1661-2112)
-extern "C" bppo_status bppo_ppo_update(bppo_ctx *c, double lr, double ent_coef, bppo_update_metrics *m) {
-    if (!c || !c->gae_done) { if (c) c->err = "ppo_update before compute_gae"; return BPPO_ERR_ARG; }
-    // opponent pool: train on the learner rows only (ppo.rs:1696-1720); their count
-    // varies per update, so each epoch's swap targets come from the sequential
-    // host walk instead of the speculating shuffle engine
-    const bool opp = opp_active(c);
-    if (opp) {
-        // the opponent path permutes on this stream with the shared scratch, into the
-        // context's own buffer, after anything still queued on fy_stream
-        if (c->fy_done > 0) BPPO_HIP(c, hipStreamWaitEvent(c->stream, c->fy_ev[c->fy_done - 1], 0));
-        c->fy_slot = -1; c->fy_done = 0;
-        c->d_perm = c->d_perm_base;
-        TRY(opp_compact_valid(c));
-    }
-    if (!opp && c->shuf_slot < 0) c->shuf_slot = c->shuf.ensure(c->rng_pos);
-    const int slot = c->shuf_slot;
-    const size_t B = opp ? (size_t)c->n_valid : (size_t)c->T * c->N;
-    std::vector<uint32_t> Jh(opp ? std::max<size_t>(B, 1) * c->cfg.num_epochs : 0);
-    uint64_t opp_pos = c->rng_pos;
-    const int M = c->cfg.num_minibatches;
-    const size_t base_mb = B / M, rem = B % M;
-    const int np = (int)c->net.n_params;
-    const int NM = WM_COUNT;
-    std::vector<float> rows;          // per minibatch: NM metric sums + 4 adv stats
-    int epochs_run = 0;
-    bool stop = false;
-    double wait_ms = 0.0;
-    TRY(tm_begin(c, TM_UPDATE));
-    // mode 1 copies d_val / d_ret on ev_stream beside the update: on every return from here
-    // the context stream waits for those copies, so the next rollout cannot overwrite the
-    // buffers under them (the normal path enqueues the wait itself below)
-    struct EvCopyGuard {
-        bppo_ctx *c; bool armed = false;
-        ~EvCopyGuard() { if (armed) (void)hipStreamWaitEvent(c->stream, c->ev_copied, 0); }
-    } ev_guard{c};
-    if (c->ev_mode == 1) { TRY(ev_reference_begin(c, opp ? c->d_valid : nullptr)); ev_guard.armed = true; }
-    TRY(popart_update_begin(c, opp ? c->d_valid : nullptr));   // ppo.rs:1787-1808
-    if (c->d_rowA && !c->rows_packed) TRY(launch_pack_rows(c));
-    c->rows_packed = false;
-    float fw_ms = 0, sh_ms = 0;
-    // without a KL early stop or a host all-reduce nothing in the loop needs the
-    // metrics on the host: the minibatches are enqueued back to back and the rows
-    // are read once after the last one (no per-minibatch stream drain)
-    const bool deferred = c->cfg.target_kl < 0 && !(c->allreduce && c->world > 1 && !c->allreduce_async);
-    int nrow = 0;
-    // the deferred path times the update's last minibatch that runs: sizes do not grow with
-    // the slot index, so it is slot M-1 unless B < M (then rem-1; none when B == 0); lockstep
-    // slots (W > 1) all run
-    const int last_run_mb = (base_mb > 0 || (c->allreduce && c->world > 1)) ? M - 1 : (int)rem - 1;
-    bool fw_recorded = false;
-    bool first_mb = true;                 // the update's first minibatch: the rollout's parameters
-    size_t rows_done = 0;                 // rows of the KL-stopped epoch's minibatches that ran
-    for (int ep = 0; ep < c->cfg.num_epochs && !stop; ep++) {
-        epochs_run++;
-        hipEvent_t s0 = c->ev[TM_SHUFFLE][0], s1 = c->ev[TM_SHUFFLE][1];
-        if (opp) {
-            uint32_t *J = Jh.data() + (size_t)ep * B;
-            auto w0 = std::chrono::steady_clock::now();
-            opp_pos = shuffle_walk_host(c->rng_key, c->cfg.rng_stream, opp_pos, (uint32_t)B, J);   // ppo.rs:1816
-            wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-            BPPO_HIP(c, hipMemcpyAsync(c->d_Jopp, J, sizeof(uint32_t) * B, hipMemcpyHostToDevice, c->stream));
-            BPPO_HIP(c, hipEventRecord(s0, c->stream));
-            if (B) TRY(launch_fisher_yates(c, c->d_Jopp, (uint32_t)B));
-            if (B) TRY(opp_map_perm(c, (uint32_t)B));
-            BPPO_HIP(c, hipEventRecord(s1, c->stream));
-        } else {
-            if (slot != c->fy_slot || ep >= c->fy_done) {
-                auto w0 = std::chrono::steady_clock::now();
-                c->shuf.wait_epoch(slot, ep);
-                wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-            }
-            TRY(fy_enqueue_ready(c, slot));          // this epoch and any other resolved since
-            BPPO_HIP(c, hipStreamWaitEvent(c->stream, c->fy_ev[ep], 0));
-            c->d_perm = c->d_perm_ep + (size_t)ep * B;
-        }
-        // no learner rows (opponent pool): the reference shuffles an empty index
-        // list (no RNG words) and skips every minibatch (ppo.rs:1815-1831).  W > 1: the
-        // ranks' learner-row counts differ, so every rank runs all M minibatch slots of
-        // every epoch in lockstep (one all-reduce each); a rank whose slot is empty adds a
-        // zero gradient and zero metric partials (oracle/ppo.c or_trainers_update)
-        const bool lockstep = c->allreduce && c->world > 1;
-        if (B == 0 && !lockstep) continue;
-        if (B) TRY(launch_epoch_adv_stats(c, (uint32_t)B, M, opp ? nullptr : c->d_inv_ep + (size_t)ep * B));
-        size_t start = 0;
-        for (int mb = 0; mb < M; mb++) {
-            const size_t sz = base_mb + ((size_t)mb < rem ? 1 : 0);
-            if (sz == 0 && !lockstep) continue;
-            // the "minibatch" phase time is the last minibatch's (read after the update in the
-            // deferred path): only that one is bracketed there -- each timestamp marker on the
-            // stream costs a few us of idle compute stream
-            const bool fw_timed = !deferred || (ep == c->cfg.num_epochs - 1 && mb == last_run_mb);
-            if (fw_timed) BPPO_HIP(c, hipEventRecord(c->ev[TM_FWDBWD][0], c->stream));
-            c->d_mb_cur = c->d_mb_stats + 4 * mb;
-            // Adam's bias corrections for this step (burn-optim: per tensor, f32 powers)
-            float c1[64], c2[64];
-            for (int t = 0; t < 2 * c->net.n_layers; t++) {
-                int ti = ++c->adam_t[t];
-                c1[t] = 1.0f - powi_f32(0.9f, ti);
-                c2[t] = 1.0f - powi_f32(0.999f, ti);
-            }
-            float *metric_dst = c->d_rows + (size_t)nrow * (NM + 4);
-            const bool multi = c->allreduce && c->world > 1;
-            if (sz == 0) {                 // lockstep slot without rows on this rank
-                BPPO_HIP(c, hipMemsetAsync(c->d_grad, 0, sizeof(float) * ((size_t)np + 64), c->stream));   // + tail
-                BPPO_HIP(c, hipMemsetAsync(c->d_mb_cur, 0, sizeof(float) * 4, c->stream));
-                // value_error_max of no rows: -inf, as the oracle's (the metric row reads the
-                // rank-local copy; the summed slot GRAD_VEMAX is not read)
-                static const float ninf = -INFINITY;
-                BPPO_HIP(c, hipMemcpyAsync(c->d_grad + np + GRAD_VEMAX_LOCAL, &ninf, sizeof(float),
-                                           hipMemcpyHostToDevice, c->stream));
-            } else if (c->wide) {
-                if (c->dbg_params && nrow < c->dbg_params_max)   // parity hook: this minibatch's parameters
-                    BPPO_HIP(c, hipMemcpyAsync(c->dbg_params + (size_t)nrow * np, c->d_params, sizeof(float) * np,
-                                               hipMemcpyDeviceToHost, c->stream));
-                TRY(wide_minibatch(c, (uint32_t)start, (uint32_t)sz, ent_coef, first_mb));
-            } else {
-                if (c->dbg_params && nrow < c->dbg_params_max)
-                    BPPO_HIP(c, hipMemcpyAsync(c->dbg_params + (size_t)nrow * np, c->d_params, sizeof(float) * np,
-                                               hipMemcpyDeviceToHost, c->stream));
-                TRY(launch_minibatch(c, (uint32_t)start, (uint32_t)sz, (float)ent_coef, first_mb));
-            }
-            if (fw_timed) { BPPO_HIP(c, hipEventRecord(c->ev[TM_FWDBWD][1], c->stream)); fw_recorded = true; }
-            first_mb = false;
-            if (multi) {
-                if (!c->allreduce_async) BPPO_HIP(c, sync_stream(c));
-                if (c->allreduce(c->d_grad, (size_t)np + NM, c->allreduce_user) != 0) {
-                    c->err = "all-reduce callback failed";
-                    return BPPO_ERR_COMM;
-                }
-            }
-            // clip + Adam; the metric row (grad[np .. np+NM) and adv stats) into the
-            // update's device rows
-            TRY(launch_adam(c, (float)lr, c1, c2, metric_dst, NM));
-            if (c->wide) TRY(wide_pack(c));
-            nrow++;
-            if (!deferred) {
-                std::vector<float> row(NM + 4);
-                BPPO_HIP(c, hipMemcpyAsync(row.data(), c->d_rows + (size_t)(nrow - 1) * (NM + 4), sizeof(float) * (NM + 4),
-                                           hipMemcpyDeviceToHost, c->stream));
-                BPPO_HIP(c, sync_stream(c));
-                float ms = 0;
-                if (event_ms(c->ev[TM_FWDBWD][0], c->ev[TM_FWDBWD][1], &ms)) fw_ms = ms;
-                if (mb == 0 && event_ms(s0, s1, &ms)) sh_ms = ms;
-                rows.insert(rows.end(), row.begin(), row.end());
-            }
-            if (!deferred && c->cfg.target_kl >= 0) {
-                const float *row = &rows[rows.size() - (NM + 4)];
-                const float n = row[10] > 0 ? row[10] : 1.0f;
-                if (row[3] / n > (float)c->cfg.target_kl) { stop = true; rows_done = start + sz; break; }   // ppo.rs:2019-2023
-            }
-            start += sz;
-        }
-    }
-    if (deferred && nrow > 0) {
-        rows.resize((size_t)nrow * (NM + 4));
-        // into pinned memory: a pageable destination makes the copy synchronous and the
-        // host thread spins in it for the whole update (a CPU the shuffle walkers need);
-        // read after the one stream wait below, behind the explained-variance pass
-        BPPO_HIP(c, hipMemcpyAsync(c->h_rows, c->d_rows, sizeof(float) * rows.size(), hipMemcpyDeviceToHost, c->stream));
-    }
-    TRY(tm_end(c, TM_UPDATE));
-    c->last_wait_ms = wait_ms;
-    c->last_walk_ms = 0.0;
-    c->last_met = 0;
-    if (opp) {
-        c->rng_pos = opp_pos;                               // the epochs walked (early stop: started ones)
-        c->last_walk_ms = wait_ms;
-        BPPO_HIP(c, hipStreamSynchronize(c->stream));      // Jh's copies done
-    } else {
-        // only started epochs consumed words (reference); windowed: the update's fixed span
-        c->rng_pos = c->shuf.win ? c->shuf.job_end(slot) : c->shuf.end_pos[slot][epochs_run - 1];
-        for (int e = 0; e < epochs_run; e++) {
-            c->last_walk_ms += c->shuf.walk_ms[slot][e];
-            c->last_met += c->shuf.coalesced[slot][e] >= 0 && e > 0;
-        }
-        c->last_spec_mwords = (double)c->shuf.spec_words.exchange(0) * 1e-6;
-        c->last_true_mwords = (double)c->shuf.true_words.exchange(0) * 1e-6;
-        c->last_walk_cpu_ms = (double)c->shuf.tsc_walk.exchange(0) / tsc_per_ms();
-        c->last_words_cpu_ms = (double)c->shuf.tsc_words.exchange(0) / tsc_per_ms();
-        c->shuf_slot = -1;
-        // this update's reads of the J slot are enqueued (fy_stream's too: epochs
-        // permuted ahead but not run after a KL early stop); the next update's
-        // shuffles begin after its rollout's T*N*A Gumbel words (usually chained already)
-        if (c->fy_slot == slot && c->fy_done > 0)
-            BPPO_HIP(c, hipStreamWaitEvent(c->stream, c->fy_ev[c->fy_done - 1], 0));
-        c->fy_slot = -1;
-        c->fy_done = 0;
-        BPPO_HIP(c, c->shuf.release(slot, c->stream));
-        c->shuf.ensure(c->rng_pos + (uint64_t)c->T * c->N * (uint64_t)c->A);
-    }
-    TRY(popart_target_stats(c, stop ? epochs_run - 1 : epochs_run, rows_done, opp ? c->d_valid : nullptr));
-    TRY(launch_explained_variance(c, opp ? c->d_valid : nullptr));
-    // mode 1: nothing after this update (the next rollout) overwrites the copied buffers early
-    if (ev_guard.armed) { ev_guard.armed = false; BPPO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_copied, 0)); }
-    BPPO_HIP(c, hipEventRecord(c->ev_upd, c->stream));      // end of this update's work
-    if (c->prefetch_next) {
-        // bppo_train_steps: the next rollout goes in behind this update (it needs only the
-        // updated parameters and the RNG position after this update's shuffles, both in
-        // stream / host order now); the host then waits for this update alone
-        c->prefetch_next = false;
-        c->env_step = c->prefetch_env_step;
-        TRY(collect_enqueue(c, true));
-        c->prefetched = true;
-        BPPO_HIP(c, wait_event(c, c->ev_upd));
-    } else {
-        BPPO_HIP(c, sync_stream(c));
-    }
-    if (deferred && nrow > 0) {
-        std::memcpy(rows.data(), c->h_rows, sizeof(float) * rows.size());
-        float ms = 0;
-        if (fw_recorded && event_ms(c->ev[TM_FWDBWD][0], c->ev[TM_FWDBWD][1], &ms)) fw_ms = ms;   // else 0
-        if (event_ms(c->ev[TM_SHUFFLE][0], c->ev[TM_SHUFFLE][1], &ms)) sh_ms = ms;
-    }
-    double ev4[4];
-    explained_variance_sums(c, ev4);
-    if (c->ev_thread.joinable()) c->ev_thread.join();     // mode 1: the reference's f32 sums
-    tm_read(c, TM_UPDATE);
-    if (c->mb_ev_n > 0) {                     // every minibatch kernel launch of this update
-        double sum = 0.0, ks[2] = {0.0, 0.0};
-        float lo = INFINITY, hi = 0.0f;
-        int n = 0, kn[2] = {0, 0};
-        for (int i = 0; i < c->mb_ev_n; i++) {
-            float ms = 0.0f;
-            if (!event_ms(c->mb_ev[i][0], c->mb_ev[i][1], &ms)) continue;
-            sum += ms; lo = std::min(lo, ms); hi = std::max(hi, ms); n++;
-            ks[c->mb_ev_split[i]] += ms; kn[c->mb_ev_split[i]]++;
-        }
-        if (n) { c->mb_k_mean = (float)(sum / n); c->mb_k_min = lo; c->mb_k_max = hi; }
-        c->mb_k_exact = kn[0] ? (float)(ks[0] / kn[0]) : 0.0f;
-        c->mb_k_split = kn[1] ? (float)(ks[1] / kn[1]) : 0.0f;
-        c->mb_ev_n = 0;
-    }
-    c->mb_launch = 0;
-    c->last_ms[TM_FWDBWD] = fw_ms;
-    c->last_ms[TM_SHUFFLE] = sh_ms;
-    c->last_rows = rows;
-    if (m) {
-        std::memset(m, 0, sizeof *m);
-        const int nup = (int)(rows.size() / (NM + 4));
-        float tp = 0, tv = 0, th = 0, tk = 0, tc = 0, tl = 0, tvm = 0, trm = 0, tam = 0, tas = 0;
-        float tamin = INFINITY, tamax = -INFINITY, tvem = 0, tves = 0, tvemax = -INFINITY;
-        float tav = 0, tevp = 0;
-        for (int u = 0; u < nup; u++) {
-            const float *r = &rows[(size_t)u * (NM + 4)];
-            const float n = r[10] > 0 ? r[10] : 1.0f;
-            const float pl = r[0] / n, vl = 0.5f * (r[1] / n), h = r[2] / n;
-            tp += pl; tv += vl; th += h; tk += r[3] / n; tc += r[4] / n;
-            tl += pl + vl * (float)c->cfg.value_coef + (-h) * (float)ent_coef;
-            tvm += r[5] / n; trm += r[6] / n;
-            const float vem = r[7] / n;
-            tvem += vem;
-            const double var = n > 1 ? ((double)r[8] - (double)n * vem * vem) / (double)(n - 1) : 0.0;
-            tves += sqrtf((float)std::max(var, 0.0));
-            tvemax = std::max(tvemax, r[9]);
-            tav += r[WM_VALID] / n;
-            tevp += r[WM_NCHOICE] > 0 ? r[WM_HV] / r[WM_NCHOICE] : 0.0f;
-            tam += r[NM]; tas += r[NM + 1];
-            tamin = std::min(tamin, r[NM + 2]); tamax = std::max(tamax, r[NM + 3]);
-        }
-        // averaged over the minibatches run; none run -> 0/0 = NaN as in ppo.rs:2071-2090
-        const float n = (float)nup;
-        m->policy_loss = tp / n; m->value_loss = tv / n; m->entropy = th / n;
-        m->entropy_scaled = m->entropy / logf((float)c->A);
-        m->approx_kl = tk / n; m->clip_fraction = tc / n; m->total_loss = tl / n;
-        m->value_mean = tvm / n; m->returns_mean = trm / n;
-        m->adv_mean_raw = tam / n; m->adv_std_raw = tas / n; m->adv_min_raw = tamin; m->adv_max_raw = tamax;
-        m->value_error_mean = tvem / n; m->value_error_std = tves / n; m->value_error_max = tvemax;
-        const double Bn = (double)B;
-        const double mr = ev4[0] / Bn, vr = ev4[1] / Bn - mr * mr;
-        const double mres = ev4[2] / Bn, vres = ev4[3] / Bn - mres * mres;
-        // ppo.rs:1268-1294 (fewer than 2 rows or Var(R) < 1e-8 -> 0)
-        m->explained_variance = (B < 2 || vr < 1e-8) ? 0.0f : (float)(1.0 - vres / vr);
-        if (c->ev_mode == 1) m->explained_variance = c->ev_ref;
-        // ppo.rs:1549-1565: only envs with action masks report these (None -> 0)
-        if (c->cfg.env_kind != BPPO_ENV_CARTPOLE) { m->avg_valid_actions = tav / n; m->entropy_valid_pct = tevp / n; }
-        m->num_updates = nup; m->epochs_run = epochs_run;
-        // PopArt metrics (ppo.rs:2061-2068): None -> NaN
-        m->value_norm_target_mean = m->value_norm_target_std = NAN;
-        m->value_norm_rescale_mag = c->pa_rescale_mag;
-        if (c->cfg.normalize_values && c->pa_tcount > 0) {
-            const double mean = c->pa_tsum / c->pa_tcount, var = c->pa_tsq / c->pa_tcount - mean * mean;
-            m->value_norm_target_mean = (float)mean;
-            m->value_norm_target_std = (float)std::sqrt(std::max(var, 0.0));
-        }
-    }
-    c->collected = 0; c->gae_done = 0;
-    return BPPO_OK;
-}
-
-// One iteration of main.rs:860-947 + ppo_update in one call: the rollout, the
-// bootstrap/GAE and the update are enqueued back to back with no host wait
-// between them (bppo_collect_rollouts and bppo_compute_gae each drain the stream
-// for their results).  The rollout's device error flags are read after the update:
-// a non-finite log-prob or an empty mask returns its status then, with the update
-// already applied (the reference panics before updating; either way the run ends).
-extern "C" bppo_status bppo_train_step(bppo_ctx *c, double lr, double ent_coef, bppo_rollout_info *info,
-                                       bppo_update_metrics *m) {
-    if (!c) return BPPO_ERR_ARG;
-    const auto t0 = std::chrono::steady_clock::now();
-    c->sync_wait_ms = 0.0;
-    c->ep_entries.clear();
-    if (c->prefetched) c->prefetched = false;     // enqueued ahead by bppo_train_steps (see bppo_collect_rollouts)
-    else TRY(collect_enqueue(c, info != nullptr));
-    TRY(gae_enqueue(c));
-    const bppo_status us = bppo_ppo_update(c, lr, ent_coef, m);   // drains the stream at its end
-    if (us == BPPO_OK) { if (!c->wide) tm_read(c, TM_BOOT); tm_read(c, TM_GAE); }
-    const bppo_status cs = collect_finish(c, info, c->coll_slot);
-    // host time in the call outside stream waits: enqueue work + engine waits
-    c->last_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() -
-                      c->sync_wait_ms;
-    c->last_sync_ms = c->sync_wait_ms;
-    return cs != BPPO_OK ? cs : us;
-}
-
-// n iterations of bppo_train_step in one call, software-pipelined: each update's
-// last stream wait covers that update only, with the next iteration's rollout
-// already enqueued behind it, so the GPU never idles between iterations (the
-// host tail of one update, the caller and the next enqueue ran in that gap).
-// Results are those of n sequential bppo_train_step calls with lr[k], ent[k] and
-// the env step global_step0 + k*T*N; nothing is left pending when it returns.
-// phase_keys/phase_sums (optional): bppo_last_kernel_ms of each key summed over the n.
-extern "C" bppo_status bppo_train_steps(bppo_ctx *c, int32_t n, const double *lr, const double *ent_coef,
-                                        uint64_t global_step0, bppo_rollout_info *infos, bppo_update_metrics *ms,
-                                        const char *const *phase_keys, int32_t nkeys, float *phase_sums) {
-    if (!c || n < 0 || !lr || !ent_coef || (nkeys > 0 && (!phase_keys || !phase_sums))) return BPPO_ERR_ARG;
-    for (int k = 0; k < nkeys; k++) phase_sums[k] = 0.0f;
-    c->ep_entries.clear();
-    const uint64_t TN = (uint64_t)c->T * c->N * (uint64_t)c->world;   // the job's env steps per iteration
-    for (int32_t k = 0; k < n; k++) {
-        const auto t0 = std::chrono::steady_clock::now();
-        c->sync_wait_ms = 0.0;
-        if (!c->prefetched) { c->env_step = global_step0 + (uint64_t)k * TN; TRY(collect_enqueue(c, true)); }
-        c->prefetched = false;
-        const int slot = c->coll_slot;
-        TRY(gae_enqueue(c));
-        c->prefetch_next = k + 1 < n;
-        c->prefetch_env_step = global_step0 + (uint64_t)(k + 1) * TN;
-        const bppo_status us = bppo_ppo_update(c, lr[k], ent_coef[k], ms ? &ms[k] : nullptr);
-        c->prefetch_next = false;
-        // on an error the next iteration's rollout may already be enqueued (ppo_update
-        // enqueues it before its wait): drain the stream so nothing is pending on
-        // return; that rollout stays the context's next one (prefetched), which
-        // bppo_collect_rollouts / bppo_train_step(s) then use instead of drawing another
-        if (us != BPPO_OK) { (void)sync_stream(c); c->collected = c->prefetched ? 1 : 0; return us; }
-        if (!c->wide) tm_read(c, TM_BOOT);
-        tm_read(c, TM_GAE);
-        const bppo_status cs = collect_finish(c, infos ? &infos[k] : nullptr, slot);
-        if (cs != BPPO_OK) { (void)sync_stream(c); c->collected = c->prefetched ? 1 : 0; return cs; }
-        c->last_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() -
-                          c->sync_wait_ms;
-        c->last_sync_ms = c->sync_wait_ms;
-        for (int q = 0; q < nkeys; q++) {
-            float v = 0.0f;
-            if (bppo_last_kernel_ms(c, phase_keys[q], &v) == BPPO_OK) phase_sums[q] += v;
-        }
-    }
     return BPPO_OK;
 }
 
@@ -1600,6 +924,22 @@ extern "C" bppo_status bppo_debug_libm(int32_t which, int32_t device, const floa
         hipMemcpy(y, dy, n * 4, hipMemcpyDeviceToHost) == hipSuccess)
         s = BPPO_OK;
     return s;
+}
+
+// the update's metric fold on caller-given rows (no HIP call)
+extern "C" bppo_status bppo_debug_fold_metrics(const float *rows, int32_t nup, const bppo_debug_fold_args *args,
+                                               bppo_update_metrics *out) {
+    if (!args || !out || nup < 0 || (!rows && nup)) return BPPO_ERR_ARG;
+    FoldArgs a;
+    a.value_coef = args->value_coef; a.ent_coef = args->ent_coef;
+    a.A = args->A; a.env_kind = args->env_kind; a.B = (size_t)args->B;
+    std::memcpy(a.ev4, args->ev4, sizeof a.ev4);
+    a.ev_mode = args->ev_mode; a.ev_ref = args->ev_ref; a.epochs_run = args->epochs_run;
+    a.normalize_values = args->normalize_values != 0;
+    a.pa_tsum = args->pa_tsum; a.pa_tsq = args->pa_tsq; a.pa_tcount = args->pa_tcount;
+    a.pa_rescale_mag = args->pa_rescale_mag;
+    fold_update_metrics(rows, nup, a, out);
+    return BPPO_OK;
 }
 
 // shuffle parity hooks: the host draw chain alone, and the device Fisher-Yates

@@ -531,6 +531,11 @@ struct bppo_ctx {
 
 // a state setter drops a rollout that bppo_train_steps enqueued ahead (bppo_api.hip)
 void drop_prefetch(bppo_ctx *c);
+// wait for the context stream with a sleeping poll (bppo_api.hip)
+hipError_t sync_stream(bppo_ctx *c);
+// the last rollout's kept episode records in the reference's order; *cnt = the device count
+// (train_loop.hip)
+bppo_status rollout_records_sorted(bppo_ctx *c, std::vector<bppo::EpisodeRec> &recs, int32_t *cnt);
 
 namespace bppo {
 // runtime switches: every BPPO_* variable is read through these two

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bppo_device.h"
+#include "bppo_metric_row.h"
 
 namespace bppo {
 
@@ -80,10 +81,7 @@ struct SampleArgs {
     double pa_mean = 0.0, pa_std = 1.0;
 };
 
-// metric slots written after the gradient (d_grad[np + k]); the first 11 are
-// shared with the CartPole kernel (k_update.hip M_*)
-enum { WM_PL = 0, WM_VL, WM_H, WM_KL, WM_CF, WM_V, WM_R, WM_VE, WM_VE2, WM_VEMAX, WM_N, WM_VALID, WM_HV,
-       WM_NCHOICE, WM_COUNT };
+// (the metric slots WM_* written after the gradient, d_grad[np + k]: bppo_metric_row.h)
 
 struct LossArgs {
     const uint32_t *perm;

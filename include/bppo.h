@@ -641,6 +641,26 @@ bppo_status bppo_debug_libm(int32_t which, int32_t device, const float *x, float
  * created since is destroyed. */
 bppo_status bppo_debug_device_memory(int64_t *live_allocations, int64_t *live_bytes);
 
+/* The update's metric fold alone: rows[nup][row_width] as bppo_minibatch_rows returns them
+ * (one row per minibatch that ran) -> *out, by the function bppo_ppo_update itself calls.
+ * B: the rows the update trained on; ev4: sum R, sum R^2, sum (R - V), sum (R - V)^2 over
+ * them in f64 (explained variance), or ev_mode = 1 and the value to report in ev_ref; the
+ * pa_* fields are PopArt's target sums, read when normalize_values != 0.
+ * No HIP call: works without a GPU. */
+typedef struct {
+    float value_coef, ent_coef;
+    int32_t A, env_kind;         /* action count; BPPO_ENV_* */
+    uint64_t B;
+    double ev4[4];
+    int32_t ev_mode;
+    float ev_ref;
+    int32_t epochs_run, normalize_values;
+    double pa_tsum, pa_tsq, pa_tcount;
+    float pa_rescale_mag;
+} bppo_debug_fold_args;
+bppo_status bppo_debug_fold_metrics(const float *rows, int32_t nup, const bppo_debug_fold_args *args,
+                                    bppo_update_metrics *out);
+
 /* shuffle parity hooks (ppo.rs:1816, rand 0.8.5 SliceRandom::shuffle on StdRng):
  * the host draw chain alone — J[i] = gen_range(0..i+1) for i = n-1..1 from word
  * position word_pos of StdRng(seed) stream `stream`, *end_pos = position after —

@@ -76,8 +76,8 @@ def _check_minibatch_rows(rows, fx, mb, pl_mag, first_epoch_rows):
     amplifies (CfgC: approx_kl 2-7x the bar from minibatch 8 of 24, profiles/r06e/), and
     test_bench_minibatches_from_device_parameters holds EVERY minibatch at 1e-5 from the
     device's own parameters.  At the benched
-    minibatch sizes and with the benched arithmetic: CfgB the exact f32 kernel on the first
-    minibatch and k_minibatch_split after; CfgC / CfgD the exact forward with f32 split-K
+    minibatch sizes and with the benched arithmetic: CfgB k_minibatch_split<true> (exact f32
+    forward, split-bf16 backward) on the first minibatch and k_minibatch_split after; CfgC / CfgD the exact forward with f32 split-K
     weight gradients and the split-bf16 backward on the first minibatch, the split-bf16 GEMMs
     on the rest (>= 32,768 rows).  Each minibatch runs from the device's own parameters after
     its earlier Adam steps (ppo.rs:1923-1988).  Floors as for the update's metrics: the
@@ -205,8 +205,8 @@ def test_bench_minibatches_from_device_parameters(case):
     permutation, "perm_ep:<e>"): the device's statistics (bppo_minibatch_rows) against
     or_minibatch_loss_grad's (ppo.rs:1923-1988; forward + loss, per-minibatch advantage
     normalization ppo.rs:1905-1913) at 1e-5 with the update metrics' floors.  This pins the
-    arithmetic the bench runs at the sizes it runs -- CfgB's 2,097,152-row minibatches (the
-    exact kernel, then k_minibatch_split), CfgC's 262,144 and CfgD's 524,288 (the first
+    arithmetic the bench runs at the sizes it runs -- CfgB's 2,097,152-row minibatches
+    (k_minibatch_split<true>: exact forward, split backward; then k_minibatch_split), CfgC's 262,144 and CfgD's 524,288 (the first
     minibatch's exact forward, then the split-bf16 GEMMs) -- without the parameter drift that
     separates the two trajectories after a few Adam steps (the fixture comparison above).
     CfgD: the first two minibatches of every epoch (the oracle's forward of a 524,288-row
