@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .ppo import Context
+from .ppo import Context, _pack_models
 
 # E::EVAL_TEMP and E::EVAL_TEMP_CUTOFF (connect_four.rs:219-221, liars_dice.rs:454,
 # skull.rs:1052; the trait's defaults are 0.3 and None, env.rs:53-58)
@@ -169,24 +169,6 @@ class EvalStats:
             out.update(length_mean=sum(self.episode_lengths) / len(self.episode_lengths),
                        length_min=min(self.episode_lengths), length_max=max(self.episode_lengths))
         return out
-
-
-def _pack_models(ctx, models, normalizers):
-    """models[k]: a flat parameter vector or None (the random player); normalizers[k]:
-    (mean, m2, count) or None -> the arrays of bppo_evaluate / bppo_evaluate_pods"""
-    K, D = len(models), ctx.obs_dim
-    params = np.zeros((K, ctx.n_params), np.float32)
-    is_random = np.zeros(K, np.int32)
-    mean = np.zeros((K, D)); m2 = np.zeros((K, D)); cnt = np.zeros(K)
-    for k, m in enumerate(models):
-        if m is None:
-            is_random[k] = 1
-        else:
-            params[k] = np.asarray(m, np.float32).reshape(-1)
-        nm = normalizers[k] if normalizers else None
-        if nm is not None:
-            mean[k], m2[k], cnt[k] = nm
-    return params, mean, m2, cnt, is_random
 
 
 def _eval_config(num_games, num_envs, temp_schedule, seed, max_steps):

@@ -24,6 +24,25 @@ from . import _lib as L
 from .host import ENV_DIMS, make_config, orthogonal_init, schedule_get, shaping_schedule, to_struct
 
 
+def _pack_models(ctx, models, normalizers):
+    """models[k]: a flat parameter vector or None (the random player); normalizers[k]:
+    (mean, m2, count) or None -> the arrays of bppo_evaluate / bppo_evaluate_pods /
+    bppo_opponents_set (at least one row each, so K = 0 still passes valid pointers)"""
+    K, D, R = len(models), ctx.obs_dim, max(len(models), 1)
+    params = np.zeros((R, ctx.n_params), np.float32)
+    is_random = np.zeros(R, np.int32)
+    mean = np.zeros((R, D)); m2 = np.zeros((R, D)); cnt = np.zeros(R)
+    for k, m in enumerate(models):
+        if m is None:
+            is_random[k] = 1
+        else:
+            params[k] = np.asarray(m, np.float32).reshape(-1)
+        nm = normalizers[k] if normalizers else None
+        if nm is not None:
+            mean[k], m2[k], cnt[k] = nm
+    return params, mean, m2, cnt, is_random
+
+
 class Context:
     """Owns one bppo_ctx (device buffers, env state, params, Adam, RNG)."""
 
@@ -145,12 +164,10 @@ class Context:
         loaded opponents, norms[k] = (mean, m2, count) or None, seat state of envs
         [0, num_opponent_envs) (EnvState, opponent_pool.rs:80-124), current_opp
         [P - 1] = OpponentPool::sample_all_slots."""
-        params = np.ascontiguousarray(params, np.float32).reshape(-1, self.n_params)
-        K, D, P = params.shape[0], self.obs_dim, self.seats
-        mean = np.zeros((max(K, 1), D)); m2 = np.zeros((max(K, 1), D)); cnt = np.zeros(max(K, 1))
-        for k, nm in enumerate(norms or []):
-            if nm is not None:
-                mean[k], m2[k], cnt[k] = nm
+        models = np.asarray(params, np.float32).reshape(-1, self.n_params)
+        K = len(models)
+        norms = list(norms or [])
+        params, mean, m2, cnt, _ = _pack_models(self, models, norms + [None] * (K - len(norms)))
         lp = np.ascontiguousarray(learner_pos, np.int32)
         po = np.ascontiguousarray(pos_to_opp, np.int32)
         co = np.ascontiguousarray(current_opp, np.int32)

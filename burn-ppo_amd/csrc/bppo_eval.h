@@ -5,7 +5,14 @@
 // device intrinsics; plain operators on the host, built with -ffp-contract=off).
 // Subnormal exp results must survive: nothing on this path flushes f32 denormals
 // (hipcc's default kernel mode keeps them; the Makefile does not ask for flushing).
+// At the end, the host steps the two evaluation loops share: a pod's RNG key and env
+// seed base, the staging of recorded games.
 #pragma once
+#include <algorithm>
+#include <cstring>
+#include <vector>
+#include "../../include/bppo.h"
+#include "bppo_device.h"
 #include "bppo_math.h"
 
 namespace bppo_eval {
@@ -92,6 +99,38 @@ BPPO_HD int sample_with_temperature(float (&x)[A], int first_valid, float temp, 
         if (!found && r < cum) { res = a; found = true; }
     }
     return res;
+}
+
+// ---- host steps shared by the two evaluation loops (eval.hip, eval_cartpole.hip) ----
+
+// A pod's StdRng::seed_from_u64(seed): its key, and base_seed = rng.next_u64(), words 0 and
+// 1, low word first, which seeds the pod's envs (env j: base_seed + j); the pod's sampling
+// draws follow from word 2 (eval.rs:1646-1648)
+inline bppo::Key8 pod_key(uint64_t seed, uint64_t *base_seed) {
+    const bppo::Key8 key = bppo::seed_key(seed);
+    uint32_t blk0[16];
+    bppo::chacha12_block(key, 0, 0, blk0);
+    *base_seed = ((uint64_t)blk0[1] << 32) | (uint64_t)blk0[0];
+    return key;
+}
+
+// The recorded games out: pod k's first min(n_games[k], cap) games go to games[k cap_per_pod
+// ...] and nothing else is written there.  On the device the pods are cap apart, so one copy
+// stages them all; a lone pod's need no staging.  The stream is drained on return.
+inline hipError_t fetch_pod_games(hipStream_t st, const bppo_eval_game *d_games, int n_pods, int cap,
+                                  const int32_t *n_games, bppo_eval_game *games, int cap_per_pod) {
+    std::vector<bppo_eval_game> h_games(n_pods > 1 ? (size_t)n_pods * cap : 0);
+    const size_t ncopy = n_pods > 1 ? h_games.size() : (size_t)std::min<int>(n_games[0], cap);
+    if (ncopy == 0) return hipSuccess;
+    hipError_t e = hipMemcpyAsync(n_pods > 1 ? h_games.data() : games, d_games, sizeof(bppo_eval_game) * ncopy,
+                                  hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return e;
+    for (size_t k = 0; k * cap < h_games.size(); k++) {
+        const int ng = std::min<int>(n_games[k], cap);
+        if (ng > 0) std::memcpy(games + k * cap_per_pod, &h_games[k * cap], sizeof(bppo_eval_game) * (size_t)ng);
+    }
+    return hipSuccess;
 }
 
 }  // namespace bppo_eval

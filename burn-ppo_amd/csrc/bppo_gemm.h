@@ -1,8 +1,12 @@
 // bppo_gemm.h — launchers of the f32 MFMA GEMM engine (k_gemm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <vector>
+#include "../../include/bppo.h"
 
 namespace bppo {
+
+struct DeviceMem;
 
 constexpr int GEMM_MAX_SPLITS = 1024;   // narrow conv weight gradients (Kin x Co = 72 x 8) need ~4 blocks per CU
 
@@ -22,6 +26,28 @@ struct FwdGroupTab {
     const double *on[MAX];       // its obs normalizer block [mean D | m2 D | count]
     uint8_t has_norm[MAX];       // whether the normalizer applies (count >= 2)
     uint8_t skip[MAX];           // the random player: no forward, no tile
+};
+// K frozen models on the device (model_set.hip), the one owner of "the models of an opponent
+// pool or an evaluation": parameters [K][n_params], normalizer blocks [K][mean D | m2 D |
+// count] (pack_norm_block, bppo_norm_block.h) and the table the forward reads them through
+// (table = false: none, and no limit on K; CartPole's pods, one model each, run no forward
+// here).  upload's copies are ordered on the context's stream, after the zeroing memsets of
+// the context's allocations (a blocking hipMemcpy on the null stream would not wait for that
+// non-blocking stream), and read the caller's arrays and this struct's: both outlive the
+// stream's next drain.  release returns the buffers to the DeviceMem that upload took them
+// from, for a set that is uploaded again at another size.
+struct ModelSet {
+    int K = 0;
+    float *d_params = nullptr;
+    double *d_on = nullptr;
+    FwdGroupTab *d_tab = nullptr;
+    FwdGroupTab tab{};
+    std::vector<double> on;
+    bool any_norm = false;
+    // random_mask bit k: model k is the random player (no parameters read, no forward)
+    bppo_status upload(bppo_ctx *c, DeviceMem &buf, int K, const float *params, const double *norm_mean,
+                       const double *norm_m2, const double *norm_count, uint64_t random_mask, bool table = true);
+    void release(DeviceMem &buf);
 };
 // One layer: out rows of group k = act(X rows W_k + b_k), W_k = params[k] + woff ([K][N]), b_k =
 // params[k] + boff.  gbase and tab are device memory; [span_r0, span_r0 + span_rows) bounds

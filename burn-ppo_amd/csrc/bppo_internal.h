@@ -15,6 +15,7 @@
 #include "../../include/bppo.h"
 #include "bppo_device.h"
 #include "bppo_epstats.h"
+#include "bppo_gemm.h"
 
 namespace bppo {
 
@@ -432,10 +433,8 @@ struct bppo_ctx {
     float *d_xc = nullptr;            // rollout rows [T][N][L]
     float *d_obs_raw = nullptr;       // normalize_obs: raw obs rows [T][N][D] for the stats update
     // opponent pool (ppo.rs:537-1063): K opponent models, envs [0, n_opp) play them
-    int opp_K = 0, n_opp = 0;
-    float *d_opp_params = nullptr;    // [K][n_params]
-    double *d_opp_on = nullptr;       // [K][2D + 1] obs normalizer per model
-    std::vector<int> opp_has_norm;
+    int n_opp = 0;
+    bppo::ModelSet opp_models;        // the K models (model_set.hip)
     int32_t *d_lpos = nullptr, *d_p2o = nullptr, *d_curopp = nullptr;   // [n_opp], [n_opp][P], [P - 1]
     int32_t *d_group = nullptr, *d_gpos = nullptr;                        // per step [N]
     float *d_valid = nullptr;         // learner-turn flags [T][N]
@@ -597,10 +596,22 @@ bppo_status wide_pack(bppo_ctx *c);
 bppo_status wide_forward(bppo_ctx *c, int rows, const float *xc, int ldxc, float *logits, float *values,
                          int split = 0);   // split: the update GEMMs on k_gemm_split (wide_minibatch)
 bppo_status wide_forward_actor(bppo_ctx *c, int rows, const float *xc, int ldxc, const float *params, float *logits);
-// the same for every model of an evaluation in one launch per layer (bppo_gemm.h FwdGroupTab)
-struct FwdGroupTab;
-bppo_status wide_forward_actor_groups(bppo_ctx *c, const int32_t *gbase, const FwdGroupTab *tab, int n_groups,
-                                      bool any_norm, int span_r0, int span_rows, float *xc, int ldxc, float *logits);
+// (model_set.hip) a ModelSet's actor forwards (bppo_gemm.h).  gb [K + 2] is the host's copy
+// of the device's d_gbase: model k owns the draw rows [gb[k + 1], gb[k + 2]) of xc [..][L],
+// overwritten by the models' normalizers, and of logits [..][A].
+// forward_models: grouped, one normalizer launch and one GEMM launch per layer for all
+// models (wide_forward_actor_groups; nets without conv layers); else one model after the
+// other (launch_obs_norm_rows_on + wide_forward_actor), bit-identical per group.
+bppo_status forward_models(bppo_ctx *c, const ModelSet &m, const int32_t *gb, const int32_t *d_gbase, float *xc,
+                           float *logits, bool grouped);
+// One env step of every mover model: src's rows [N][L] of group != 0 sorted to their draw
+// positions gpos in xc, forwarded, and their logits selected back into dst [N][A] (rows of
+// group 0 and of a random model keep what dst held).  Nothing is launched when no model has
+// a row to forward.  Conv nets take the loop (their im2col scratch holds one model's rows),
+// every other net the grouped launches.
+bppo_status models_step_forward(bppo_ctx *c, const ModelSet &m, const int32_t *group, const int32_t *gpos,
+                                const int32_t *gb, const int32_t *d_gbase, const float *src, float *xc, float *logits,
+                                float *dst);
 // CNN trunk (cnn.hip): conv stack + flatten of `rows` obs rows -> d_cnn_f; backward
 // of the conv stack from dF (dL/d features, [rows][fdim]) into the gradient
 bppo_status cnn_alloc(bppo_ctx *c);
@@ -630,8 +641,6 @@ bppo_status opp_step_seats(bppo_ctx *c, int t);
 bppo_status opp_rollout_end(bppo_ctx *c);
 bppo_status opp_compact_valid(bppo_ctx *c);
 bppo_status opp_map_perm(bppo_ctx *c, uint32_t n);
-bppo_status opp_sort_rows(bppo_ctx *c, const int32_t *group, const int32_t *gpos, const float *src, float *dst);
-bppo_status opp_select(bppo_ctx *c, const int32_t *group, const int32_t *gpos, const float *src, float *dst);
 bppo_status wide_collect(bppo_ctx *c, uint64_t base);
 bppo_status wide_bootstrap_gae(bppo_ctx *c);
 bppo_status wide_minibatch(bppo_ctx *c, uint32_t start, uint32_t n, double ent_coef, bool first);

@@ -19,11 +19,11 @@
 //   k_eval_scan      the counts scanned model-major, pod-minor: each env's row, the header
 //   one host read    {unfinished pods, error flags, group bases}: bounds the forward's
 //                    grids and ends the loop (eval.rs:1670-1674)
-//   forward          rows sorted model-major (k_opp_sort_rows); all models at once: one
-//                    obs normalizer launch (eval.rs:1727-1734) and one GEMM launch per layer
-//                    over every model's row range, read from the header on the device
-//                    (wide_forward_actor_groups); logits selected back
-//                    (k_opp_select); a random model's rows see zero logits (eval.rs:1749-1752).
+//   forward          models_step_forward (model_set.hip), the opponent-pool rollout's too: rows
+//                    sorted model-major; all models at once, one obs normalizer launch
+//                    (eval.rs:1727-1734) and one GEMM launch per layer over every model's row
+//                    range, read from the header on the device; logits
+//                    selected back; a random model's rows see zero logits (eval.rs:1749-1752).
 //                    Nets with conv layers: one model after the other (wide_forward_actor)
 //   k_eval_sample    sample_with_temperature per row at the pod's word position + draw index
 //   env step         k_wide_step with the frozen mask, the outcome sink and per-env seeds
@@ -433,69 +433,6 @@ extern "C" bppo_status bppo_debug_eval_sample(int32_t device, int32_t A, int32_t
     return (err & EV_ERR_ZERO_SUM) ? BPPO_ERR_NONFINITE : BPPO_OK;
 }
 
-// The models of one evaluation on the device: parameters [K][n_params], normalizer blocks
-// [K][mean D | m2 D | count], and the table the grouped forward reads them through.  The
-// uploads are ordered on the context's stream and read this struct's host arrays: it
-// outlives the stream's next drain.
-struct EvalModels {
-    float *d_params = nullptr;
-    double *d_on = nullptr;
-    FwdGroupTab *d_tab = nullptr;
-    FwdGroupTab tab{};
-    std::vector<double> on;
-    bool any_norm = false;
-};
-static bppo_status upload_models(bppo_ctx *c, DeviceMem &buf, EvalModels &m, int K, const float *params,
-                                 const double *norm_mean, const double *norm_m2, const double *norm_count,
-                                 uint64_t random_models) {
-    const int D = c->D;
-    const size_t np = c->net.n_params, nb = (size_t)(2 * D + 1);
-    BPPO_HIP(c, buf.alloc(&m.d_params, np * K));
-    BPPO_HIP(c, buf.alloc(&m.d_on, nb * K));
-    BPPO_HIP(c, buf.alloc(&m.d_tab, 1));
-    m.on.assign(nb * K, 0.0);
-    for (int k = 0; k < K; k++) {
-        m.tab.params[k] = m.d_params + (size_t)k * np;
-        m.tab.on[k] = m.d_on + (size_t)k * nb;
-        m.tab.skip[k] = (uint8_t)((random_models >> k) & 1ull);
-        if (m.tab.skip[k]) continue;
-        BPPO_HIP(c, hipMemcpyAsync(m.d_params + (size_t)k * np, params + (size_t)k * np, sizeof(float) * np,
-                                   hipMemcpyHostToDevice, c->stream));
-        if (!norm_count || norm_count[k] < 2.0 || !norm_mean || !norm_m2) continue;
-        m.tab.has_norm[k] = 1;
-        m.any_norm = true;
-        std::memcpy(&m.on[(size_t)k * nb], norm_mean + (size_t)k * D, sizeof(double) * D);
-        std::memcpy(&m.on[(size_t)k * nb + D], norm_m2 + (size_t)k * D, sizeof(double) * D);
-        m.on[(size_t)k * nb + 2 * D] = norm_count[k];
-    }
-    BPPO_HIP(c, hipMemcpyAsync(m.d_on, m.on.data(), sizeof(double) * m.on.size(), hipMemcpyHostToDevice, c->stream));
-    BPPO_HIP(c, hipMemcpyAsync(m.d_tab, &m.tab, sizeof(FwdGroupTab), hipMemcpyHostToDevice, c->stream));
-    return BPPO_OK;
-}
-
-// The forward one model after the other, sized by the host's copy of the group bases gb
-// [K + 2]: the path of nets with conv layers (their im2col scratch holds one model's rows),
-// and mode 0 of bppo_debug_forward_groups.
-static bppo_status forward_models_loop(bppo_ctx *c, int K, const EvalModels &m, const int32_t *gb, float *d_oxc,
-                                       float *d_ologits) {
-    const int A = c->A, L = c->L;
-    for (int k = 0; k < K; k++) {
-        const int r0 = gb[k + 1], rows = gb[k + 2] - gb[k + 1];
-        if (rows <= 0 || m.tab.skip[k]) continue;
-        float *x = d_oxc + (size_t)r0 * L;
-        if (m.tab.has_norm[k]) TRY(launch_obs_norm_rows_on(c, rows, x + c->G, L, nullptr, m.tab.on[k]));
-        TRY(wide_forward_actor(c, rows, x, L, m.tab.params[k], d_ologits + (size_t)r0 * A));
-    }
-    return BPPO_OK;
-}
-// All models at once from the device's group bases d_gbase (nets without conv layers); the
-// host's copy gives only the span of rows.
-static bppo_status forward_models(bppo_ctx *c, int K, const EvalModels &m, const int32_t *gb, const int32_t *d_gbase,
-                                  float *d_oxc, float *d_ologits) {
-    if (c->net.n_conv) return forward_models_loop(c, K, m, gb, d_oxc, d_ologits);
-    return wide_forward_actor_groups(c, d_gbase, m.d_tab, K, m.any_norm, gb[1], gb[K + 1] - gb[1], d_oxc, c->L, d_ologits);
-}
-
 static uint64_t random_mask(const int32_t *is_random, int K) {
     uint64_t m = 0;
     for (int k = 0; k < K; k++)
@@ -521,32 +458,28 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
                                 const uint64_t *pod_seeds, const int32_t *pod_seat_model,
                                 const std::vector<int32_t> &slot_model, bppo_eval_game *games, int cap_per_pod,
                                 int32_t *n_games, uint64_t *rng_word_pos) {
-    const int P = c->Pa, N = c->N, A = c->A, D = c->D, L = c->L;
+    const int P = c->Pa, N = c->N, A = c->A, L = c->L;
     drop_prefetch(c);
     if (!c->gae_done) c->collected = 0;       // a rollout not yet bootstrapped would read the evaluation's envs
     for (int k = 0; k < n_pods; k++) n_games[k] = 0;
 
-    // per pod: StdRng(pod_seeds[k]); base_seed = rng.next_u64(), words 0 and 1, low word first,
-    // seeds its envs (eval.rs:1646-1648)
+    // per pod: StdRng(pod_seeds[k]), whose first u64 seeds its envs (bppo_eval.h pod_key)
     std::vector<Key8> keys((size_t)n_pods);
     std::vector<uint64_t> env_seed((size_t)N);
     for (int k = 0; k < n_pods; k++) {
-        keys[k] = seed_key(pod_seeds[k]);
-        uint32_t blk0[16];
-        chacha12_block(keys[k], 0, 0, blk0);
-        const uint64_t base_seed = ((uint64_t)blk0[1] << 32) | (uint64_t)blk0[0];
+        uint64_t base_seed;
+        keys[k] = bppo_eval::pod_key(pod_seeds[k], &base_seed);
         for (int j = 0; j < E; j++) env_seed[(size_t)k * E + j] = base_seed + (uint64_t)j;
     }
 
     const std::vector<int32_t> perms = generate_permutations(P);
     const int nperm = (int)(perms.size() / (size_t)P);
-    const size_t np = c->net.n_params;
 
     DeviceMem buf;   // this call's buffers, freed when it ends
     EvalState s{};
     int32_t *d_perm_tab = nullptr, *d_seat_model = nullptr, *d_slot_model = nullptr;
     float *d_oxc = nullptr, *d_ologits = nullptr;
-    EvalModels mod;
+    ModelSet mod;
     EvalOutcome *d_sink = nullptr;
     bppo_eval_game *d_games = nullptr;
     Key8 *d_keys = nullptr;
@@ -585,7 +518,7 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
     s.err = c->d_err;
 
     // models: uploads ordered on the context's stream, drained before the host arrays may go
-    TRY(upload_models(c, buf, mod, K, params, norm_mean, norm_m2, norm_count, random_models));
+    TRY(mod.upload(c, buf, K, params, norm_mean, norm_m2, norm_count, random_models));
     BPPO_HIP(c, hipMemcpyAsync(d_perm_tab, perms.data(), sizeof(int32_t) * perms.size(), hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_seat_model, pod_seat_model, sizeof(int32_t) * (size_t)n_pods * P, hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_slot_model, slot_model.data(), sizeof(int32_t) * slot_model.size(), hipMemcpyHostToDevice, c->stream));
@@ -621,14 +554,8 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
         const EvalHdr &h = *h_hdr;
         if (h.unfinished == 0) break;              // every pod: num_games games or no active env (eval.rs:1670-1674)
         if (step >= cfg->max_steps) { c->err = who + ": max_steps exceeded before every pod had played num_games games"; st = BPPO_ERR_ARG; break; }
-        const int32_t *gb = h.gbase;
-        bool any_fwd = false;
-        for (int k = 0; k < K; k++) any_fwd = any_fwd || (!((random_models >> k) & 1ull) && gb[k + 2] > gb[k + 1]);
-        if (any_fwd) {
-            TRY(opp_sort_rows(c, s.group, s.gpos, c->d_bxc, d_oxc));
-            TRY(forward_models(c, K, mod, gb, s.hdr->gbase, d_oxc, d_ologits));
-            TRY(opp_select(c, s.group, s.gpos, d_ologits, c->d_logits));
-        }
+        TRY(models_step_forward(c, mod, s.group, s.gpos, h.gbase, s.hdr->gbase, c->d_bxc, d_oxc, d_ologits,
+                                c->d_logits));
         EvalSampleArgs g;
         g.N = N; g.logits = c->d_logits; g.mask = c->d_bmask; g.group = s.group; g.didx = s.didx; g.temp = s.tempv;
         g.random_models = random_models; g.pod_envs = E; g.pod_key = d_keys; g.pod_rngpos = s.rngpos; g.stream = 0;
@@ -654,19 +581,7 @@ static bppo_status evaluate_run(bppo_ctx *c, const std::string &who, const bppo_
         BPPO_HIP(c, hipMemcpyAsync(rng_word_pos, s.rngpos, sizeof(uint64_t) * (size_t)n_pods, hipMemcpyDeviceToHost, c->stream));
     BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
     BPPO_HIP(c, hipStreamSynchronize(c->stream));
-    // pod k's played games go to games[k cap_per_pod ...] and nothing else is written there.  On
-    // the device the pods are cap apart, so one copy stages them all; a lone pod's need no staging
-    std::vector<bppo_eval_game> h_games(n_pods > 1 ? (size_t)n_pods * cap : 0);
-    const size_t ncopy = n_pods > 1 ? h_games.size() : (size_t)std::min<int>(n_games[0], cap);
-    if (ncopy > 0) {
-        BPPO_HIP(c, hipMemcpyAsync(n_pods > 1 ? h_games.data() : games, d_games, sizeof(bppo_eval_game) * ncopy,
-                                   hipMemcpyDeviceToHost, c->stream));
-        BPPO_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    for (size_t k = 0; k * cap < h_games.size(); k++) {
-        const int ng = std::min<int>(n_games[k], cap);
-        if (ng > 0) std::memcpy(games + k * cap_per_pod, &h_games[k * cap], sizeof(bppo_eval_game) * (size_t)ng);
-    }
+    BPPO_HIP(c, bppo_eval::fetch_pod_games(c->stream, d_games, n_pods, cap, n_games, games, cap_per_pod));
     if (st != BPPO_OK) return st;
     const int32_t err = h_hdr->err;
     if (err & 8) { c->err = who + ": an action outside the env's action mask"; return BPPO_ERR_ARG; }
@@ -772,18 +687,17 @@ extern "C" bppo_status bppo_debug_forward_groups(bppo_ctx *c, int32_t mode, int3
     drop_prefetch(c);
     if (!c->gae_done) c->collected = 0;       // the hidden buffers are the rollout's
     DeviceMem buf;   // this call's buffers, freed when it ends
-    EvalModels mod;
+    ModelSet mod;
     int32_t *d_gb = nullptr;
     float *d_x = nullptr, *d_l = nullptr;
     BPPO_HIP(c, buf.alloc(&d_gb, gb.size()));
     BPPO_HIP(c, buf.alloc(&d_x, (size_t)rows * L));
     BPPO_HIP(c, buf.alloc(&d_l, (size_t)rows * A));
-    TRY(upload_models(c, buf, mod, K, params, norm_mean, norm_m2, norm_count, random_models));
+    TRY(mod.upload(c, buf, K, params, norm_mean, norm_m2, norm_count, random_models));
     BPPO_HIP(c, hipMemcpyAsync(d_gb, gb.data(), sizeof(int32_t) * gb.size(), hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_x, xc, sizeof(float) * (size_t)rows * L, hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemsetAsync(d_l, 0, sizeof(float) * (size_t)rows * A, c->stream));
-    if (mode == 0) TRY(forward_models_loop(c, K, mod, gb.data(), d_x, d_l));
-    else TRY(wide_forward_actor_groups(c, d_gb, mod.d_tab, K, mod.any_norm, gb[1], gb[K + 1] - gb[1], d_x, L, d_l));
+    TRY(forward_models(c, mod, gb.data(), d_gb, d_x, d_l, mode == 1));
     BPPO_HIP(c, hipMemcpyAsync(logits, d_l, sizeof(float) * (size_t)rows * A, hipMemcpyDeviceToHost, c->stream));
     BPPO_HIP(c, hipStreamSynchronize(c->stream));
     return BPPO_OK;

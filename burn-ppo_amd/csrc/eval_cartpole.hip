@@ -280,30 +280,16 @@ extern "C" bppo_status bppo_evaluate_episodes(bppo_ctx *c, const bppo_eval_confi
                                                   : std::max(1, std::min(CE_LAUNCH_MAX_STEPS, CE_LAUNCH_ENV_STEPS / per));
     const int cap = std::min(cap_per_pod, cfg->num_games);
 
-    // per pod: StdRng::seed_from_u64(pod_seeds[k]); base_seed = next_u64(), words 0 and 1, low
-    // word first (eval.rs:1646-1648)
+    // per pod: StdRng(pod_seeds[k]) and its first u64, which seeds the pod's envs (bppo_eval.h pod_key)
     std::vector<Key8> keys((size_t)n_pods);
     std::vector<uint64_t> base_seed((size_t)n_pods);
-    std::vector<double> on((size_t)n_pods * 11, 0.0);
-    for (int k = 0; k < n_pods; k++) {
-        keys[k] = seed_key(pod_seeds[k]);
-        uint32_t blk0[16];
-        chacha12_block(keys[k], 0, 0, blk0);
-        base_seed[k] = ((uint64_t)blk0[1] << 32) | (uint64_t)blk0[0];
-        if (!norm_count || !norm_mean || !norm_m2 || norm_count[k] < 2.0) continue;
-        std::memcpy(&on[(size_t)k * 11], norm_mean + (size_t)k * 5, sizeof(double) * 5);
-        std::memcpy(&on[(size_t)k * 11 + 5], norm_m2 + (size_t)k * 5, sizeof(double) * 5);
-        on[(size_t)k * 11 + 10] = norm_count[k];
-    }
+    for (int k = 0; k < n_pods; k++) keys[k] = bppo_eval::pod_key(pod_seeds[k], &base_seed[k]);
 
     DeviceMem buf;   // this call's buffers, freed when it ends
     CpEvalArgs a{};
-    float *d_params = nullptr;
-    double *d_on = nullptr;
+    ModelSet mod;    // pod k plays model k: blocks of 2 D + 1 = 11 doubles (CpEvalArgs::on)
     Key8 *d_keys = nullptr;
     uint64_t *d_base = nullptr;
-    BPPO_HIP(c, buf.alloc(&d_params, np * n_pods));
-    BPPO_HIP(c, buf.alloc(&d_on, on.size()));
     BPPO_HIP(c, buf.alloc(&d_keys, (size_t)n_pods));
     BPPO_HIP(c, buf.alloc(&d_base, (size_t)n_pods));
     BPPO_HIP(c, buf.alloc(&a.env, N));
@@ -314,11 +300,10 @@ extern "C" bppo_status bppo_evaluate_episodes(bppo_ctx *c, const bppo_eval_confi
     a.E = E; a.num_games = cfg->num_games; a.cap = cap; a.max_steps = cfg->max_steps; a.launch_steps = launch_steps;
     a.n_params = (int)np;
     a.temp = bppo_eval::TempSched{cfg->temp_initial, cfg->temp_final, cfg->temp_cutoff, cfg->temp_decay};
-    a.params = d_params; a.on = d_on; a.key = d_keys; a.base_seed = d_base;
     // uploads ordered on the context's stream; the first header read below drains them
     // before the host arrays may go
-    BPPO_HIP(c, hipMemcpyAsync(d_params, params, sizeof(float) * np * n_pods, hipMemcpyHostToDevice, c->stream));
-    BPPO_HIP(c, hipMemcpyAsync(d_on, on.data(), sizeof(double) * on.size(), hipMemcpyHostToDevice, c->stream));
+    TRY(mod.upload(c, buf, n_pods, params, norm_mean, norm_m2, norm_count, 0, false));
+    a.params = mod.d_params; a.on = mod.d_on; a.key = d_keys; a.base_seed = d_base;
     BPPO_HIP(c, hipMemcpyAsync(d_keys, keys.data(), sizeof(Key8) * keys.size(), hipMemcpyHostToDevice, c->stream));
     BPPO_HIP(c, hipMemcpyAsync(d_base, base_seed.data(), sizeof(uint64_t) * base_seed.size(), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_cartpole_eval_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, n_pods, E,
@@ -349,16 +334,7 @@ extern "C" bppo_status bppo_evaluate_episodes(bppo_ctx *c, const bppo_eval_confi
         over = over || unfinished(k);
         err |= h.err;
     }
-    // pod k's recorded games go to games[k cap_per_pod ...] and nothing else is written there
-    if (cap > 0) {
-        std::vector<bppo_eval_game> h_games((size_t)n_pods * cap);
-        BPPO_HIP(c, hipMemcpyAsync(h_games.data(), a.games, sizeof(bppo_eval_game) * h_games.size(), hipMemcpyDeviceToHost, c->stream));
-        BPPO_HIP(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; k < n_pods; k++) {
-            const int ng = std::min<int>(n_games[k], cap);
-            if (ng > 0) std::memcpy(games + (size_t)k * cap_per_pod, &h_games[(size_t)k * cap], sizeof(bppo_eval_game) * (size_t)ng);
-        }
-    }
+    BPPO_HIP(c, bppo_eval::fetch_pod_games(c->stream, a.games, n_pods, cap, n_games, games, cap_per_pod));
     if (over) { c->err = "evaluate_episodes: max_steps exceeded before every pod had played num_games episodes"; return BPPO_ERR_ARG; }
     if (err & CE_ERR_ZERO_SUM) { c->err = "evaluate_episodes: the sampler's softmax sum was zero"; return BPPO_ERR_NONFINITE; }
     return BPPO_OK;

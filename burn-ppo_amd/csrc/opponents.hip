@@ -9,8 +9,9 @@
 //                 order within a group (the reference samples the learner batch,
 //                 then iterates a HashMap of opponent batches: its order is not
 //                 deterministic, ours is ascending)
-//   learner forward on all N rows; each model's actor forward on all N rows of
-//   its own normalized copy, its rows' logits selected into the step's logits
+//   learner forward on all N rows; the models' actor forwards on their own rows of
+//   the raw copy, sorted into draw order, each under its own obs normalizer, their
+//   logits selected into the step's logits (models_step_forward, model_set.hip)
 //   sampling (k_sample_masked) at word base + position * A
 //   env step, then k_opp_seats: the step's N*A Gumbel words, then for every
 //   finished opponent game in env order its OpponentEpisodeCompletion record and
@@ -73,23 +74,6 @@ __global__ void __launch_bounds__(OG_THREADS) k_opp_group(int N, int n_opp, int 
         const int g = group[e];
         gpos[e] = base[g] + cnt[g][tid]++;
     }
-}
-
-// the step's raw rows in draw order: each model's rows become one contiguous slice
-__global__ void k_opp_sort_rows(int N, int L, const int32_t *group, const int32_t *gpos, const float *src, float *dst) {
-    const size_t n = (size_t)N * L;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t e = i / L, k = i - e * L;
-        if (group[e] != 0) dst[(size_t)gpos[e] * L + k] = src[i];
-    }
-}
-
-// the opponents' logits (draw order) into the step's logits for their rows
-__global__ void k_opp_select(int N, int A, const int32_t *group, const int32_t *gpos, const float *src, float *dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N * A) return;
-    const int e = i / A;
-    if (group[e] != 0) dst[i] = src[(size_t)gpos[e] * A + (i - e * A)];
 }
 
 // main-stream words from an LDS window [base, end) filled in parallel by the
@@ -318,7 +302,7 @@ __global__ void k_map_perm(uint32_t n, const uint32_t *vidx, uint32_t *perm) {
     if (j < n) perm[j] = vidx[perm[j]];
 }
 
-bool opp_active(const bppo_ctx *c) { return c->wide && c->n_opp > 0 && c->opp_K > 0; }
+bool opp_active(const bppo_ctx *c) { return c->wide && c->n_opp > 0 && c->opp_models.K > 0; }
 
 bppo_status opp_alloc(bppo_ctx *c) {
     const size_t N = c->N, TN = (size_t)c->T * c->N;
@@ -358,48 +342,22 @@ bppo_status opp_step_group(bppo_ctx *c, int t) {
     const size_t r0 = (size_t)t * c->N;
     BPPO_HIP(c, hipMemcpyAsync(c->d_oraw, c->d_xc + r0 * c->L, sizeof(float) * (size_t)c->N * c->L,
                                hipMemcpyDeviceToDevice, c->stream));
-    hipLaunchKernelGGL(k_opp_group, dim3(1), dim3(OG_THREADS), 0, c->stream, c->N, c->n_opp, c->Pa, c->opp_K + 1,
+    hipLaunchKernelGGL(k_opp_group, dim3(1), dim3(OG_THREADS), 0, c->stream, c->N, c->n_opp, c->Pa, c->opp_models.K + 1,
                        c->d_players + r0, c->d_lpos, c->d_p2o, c->d_group, c->d_gpos, c->d_gbase, c->d_err);
     TRY(launch_check(c, __func__));
     // the per-model row counts size the opponents' GEMMs: one small read per step
-    BPPO_HIP(c, hipMemcpyAsync(c->h_gbase, c->d_gbase, sizeof(int32_t) * (c->opp_K + 2), hipMemcpyDeviceToHost,
+    BPPO_HIP(c, hipMemcpyAsync(c->h_gbase, c->d_gbase, sizeof(int32_t) * (c->opp_models.K + 2), hipMemcpyDeviceToHost,
                                c->stream));
     BPPO_HIP(c, hipStreamSynchronize(c->stream));
     return BPPO_OK;
 }
 
-// each model's actor forward (its own obs normalizer, ppo.rs:809-812) on all
-// rows; its rows' logits replace the learner's in d_logits
+// each model's actor forward (its own obs normalizer, ppo.rs:809-812) on its rows of the raw
+// copy; its rows' logits replace the learner's in d_logits.  Nothing runs in a step where no
+// opponent moves (model_set.hip)
 bppo_status opp_step_forwards(bppo_ctx *c) {
-    const size_t np = c->net.n_params;
-    const int32_t *gb = c->h_gbase;            // group g owns draw rows [gb[g], gb[g + 1])
-    if (gb[c->opp_K + 1] == gb[1]) return BPPO_OK;   // no opponent moves this step
-    TRY(opp_sort_rows(c, c->d_group, c->d_gpos, c->d_oraw, c->d_oxc));
-    for (int k = 0; k < c->opp_K; k++) {
-        const int r0 = gb[k + 1], rows = gb[k + 2] - gb[k + 1];
-        if (rows <= 0) continue;
-        float *x = c->d_oxc + (size_t)r0 * c->L;
-        if (c->opp_has_norm[k])
-            TRY(launch_obs_norm_rows_on(c, rows, x + c->G, c->L, nullptr, c->d_opp_on + (size_t)k * (2 * c->D + 1)));
-        TRY(wide_forward_actor(c, rows, x, c->L, c->d_opp_params + (size_t)k * np, c->d_ologits + (size_t)r0 * c->A));
-    }
-    return opp_select(c, c->d_group, c->d_gpos, c->d_ologits, c->d_logits);
-}
-
-// the two row movers, also used by the evaluation loop (eval.hip): rows of group 0 stay
-bppo_status opp_sort_rows(bppo_ctx *c, const int32_t *group, const int32_t *gpos, const float *src, float *dst) {
-    const size_t n = (size_t)c->N * c->L;
-    hipLaunchKernelGGL(k_opp_sort_rows, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0,
-                       c->stream, c->N, c->L, group, gpos, src, dst);
-    TRY(launch_check(c, __func__));
-    return BPPO_OK;
-}
-bppo_status opp_select(bppo_ctx *c, const int32_t *group, const int32_t *gpos, const float *src, float *dst) {
-    const int n = c->N * c->A;
-    hipLaunchKernelGGL(k_opp_select, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->N, c->A, group, gpos, src,
-                       dst);
-    TRY(launch_check(c, __func__));
-    return BPPO_OK;
+    return models_step_forward(c, c->opp_models, c->d_group, c->d_gpos, c->h_gbase, c->d_gbase, c->d_oraw, c->d_oxc,
+                               c->d_ologits, c->d_logits);
 }
 
 bppo_status opp_step_seats(bppo_ctx *c, int t) {
@@ -454,8 +412,7 @@ extern "C" bppo_status bppo_opponents_set(bppo_ctx *c, int32_t n_models, const f
         c->err = "opponent pool: models and seat state required";
         return BPPO_ERR_ARG;
     }
-    const int P = c->Pa, D = c->D;   // EnvState seats: the active player count (main.rs:552, 649)
-    const size_t np = c->net.n_params;
+    const int P = c->Pa;   // EnvState seats: the active player count (main.rs:552, 649)
     if (num_opponent_envs > 0) {
         for (int e = 0; e < num_opponent_envs; e++) {
             if (learner_pos[e] < 0 || learner_pos[e] >= P) { c->err = "opponent pool: learner_pos out of range"; return BPPO_ERR_ARG; }
@@ -475,31 +432,16 @@ extern "C" bppo_status bppo_opponents_set(bppo_ctx *c, int32_t n_models, const f
     TRY(opp_records_clear(c));
     BPPO_HIP(c, hipMemsetAsync(c->d_ep_count, 0, 4, c->stream));
     // the buffers sized by this call
-    (void)c->mem.release(c->d_opp_params);
-    (void)c->mem.release(c->d_opp_on);
+    c->opp_models.release(c->mem);
     (void)c->mem.release(c->d_lpos);
     (void)c->mem.release(c->d_p2o);
-    c->opp_K = n_models;
     c->n_opp = num_opponent_envs;
-    c->opp_has_norm.assign(std::max(n_models, 1), 0);
-    BPPO_HIP(c, c->zalloc(&c->d_opp_params, np * std::max(n_models, 1)));
-    BPPO_HIP(c, c->zalloc(&c->d_opp_on, (size_t)(2 * D + 1) * std::max(n_models, 1)));
     BPPO_HIP(c, c->zalloc(&c->d_lpos, (size_t)std::max(num_opponent_envs, 1)));
     BPPO_HIP(c, c->zalloc(&c->d_p2o, (size_t)std::max(num_opponent_envs, 1) * P));
     // uploads are ordered on the context stream after the allocations' zeroing memsets (a
     // blocking hipMemcpy on the null stream would not wait for that non-blocking
     // stream); the stream is drained before the host arrays may go away
-    if (n_models > 0)
-        BPPO_HIP(c, hipMemcpyAsync(c->d_opp_params, params, sizeof(float) * np * n_models, hipMemcpyHostToDevice, c->stream));
-    std::vector<double> on((size_t)(2 * D + 1) * std::max(n_models, 1), 0.0);
-    for (int k = 0; k < n_models; k++) {
-        if (!norm_count || norm_count[k] < 2.0 || !norm_mean || !norm_m2) continue;
-        c->opp_has_norm[k] = 1;
-        std::memcpy(&on[(size_t)k * (2 * D + 1)], norm_mean + (size_t)k * D, sizeof(double) * D);
-        std::memcpy(&on[(size_t)k * (2 * D + 1) + D], norm_m2 + (size_t)k * D, sizeof(double) * D);
-        on[(size_t)k * (2 * D + 1) + 2 * D] = norm_count[k];
-    }
-    BPPO_HIP(c, hipMemcpyAsync(c->d_opp_on, on.data(), sizeof(double) * on.size(), hipMemcpyHostToDevice, c->stream));
+    TRY(c->opp_models.upload(c, c->mem, n_models, params, norm_mean, norm_m2, norm_count, 0));
     if (num_opponent_envs > 0) {
         BPPO_HIP(c, hipMemcpyAsync(c->d_lpos, learner_pos, sizeof(int32_t) * num_opponent_envs, hipMemcpyHostToDevice, c->stream));
         BPPO_HIP(c, hipMemcpyAsync(c->d_p2o, pos_to_opp, sizeof(int32_t) * (size_t)num_opponent_envs * P,
@@ -548,7 +490,7 @@ extern "C" bppo_status bppo_opponents_results(bppo_ctx *c, int32_t *wins, int32_
     OppResults r;
     BPPO_HIP(c, hipMemcpyAsync(&r, c->d_opp_res, sizeof r, hipMemcpyDeviceToHost, c->stream));
     BPPO_HIP(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < c->opp_K; k++) {
+    for (int k = 0; k < c->opp_models.K; k++) {
         if (wins) wins[k] = r.wins[k];
         if (games) games[k] = r.games[k];
         if (swiss_points) swiss_points[k] = (int64_t)r.swiss[k];

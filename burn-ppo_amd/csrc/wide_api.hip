@@ -170,64 +170,6 @@ bppo_status wide_forward_actor(bppo_ctx *c, int rows, const float *xc, int ldxc,
     return BPPO_OK;
 }
 
-// The obs normalizers of the grouped forward (k_obs_norm_rows's arithmetic per element):
-// 8 rows per block, 32 threads per row; a row's group is found by walking gbase, its
-// normalizer block and has-normalizer flag come from the table.
-__global__ void __launch_bounds__(256) k_obs_norm_groups(const int32_t *gbase, const FwdGroupTab *tab, int n_groups,
-                                                         int D, int ld, float *x, float clip) {
-    const int row = gbase[1] + (int)blockIdx.x * 8 + ((int)threadIdx.x >> 5);
-    if (row >= gbase[n_groups + 1]) return;
-    int g = 0;
-    while (g + 1 < n_groups && row >= gbase[g + 2]) g++;   // group g owns [gbase[g + 1], gbase[g + 2])
-    if (tab->skip[g] || !tab->has_norm[g]) return;
-    const double *on = tab->on[g];
-    const double cnt = on[2 * D];
-    if (!(cnt >= 2.0)) return;
-    for (int d = threadIdx.x & 31; d < D; d += 32) {
-        float *p = x + (size_t)row * ld + d;
-        const float v = *p;
-        double sd = sqrt(on[D + d] / cnt);
-        sd = sd < 1e-8 ? 1e-8 : sd;
-        float z = (float)(((double)v - on[d]) / sd);
-        z = z < -clip ? -clip : z;
-        z = z > clip ? clip : z;
-        *p = z;
-    }
-}
-
-// wide_forward_actor for all the models of an evaluation at once (nets without conv layers):
-// model k's rows are [gbase[k + 1], gbase[k + 2]) of the sorted row buffer xc (and of logits,
-// and of the hidden buffers); gbase and tab are device memory.  One normalizer launch (if any
-// model has one) and one GEMM launch per layer, whatever the number of models; the host gives
-// only the span of rows that bounds the groups.  Per group bit-identical to
-// launch_obs_norm_rows_on + wide_forward_actor on that group's rows.
-bppo_status wide_forward_actor_groups(bppo_ctx *c, const int32_t *gbase, const FwdGroupTab *tab, int n_groups,
-                                      bool any_norm, int span_r0, int span_rows, float *xc, int ldxc, float *logits) {
-    const NetLayout &n = c->net;
-    if (n.n_conv) { c->err = "wide_forward_actor_groups: no conv layers"; return BPPO_ERR_UNSUPPORTED; }
-    if (span_rows <= 0) return BPPO_OK;
-    if (span_r0 < 0 || span_r0 + span_rows > c->rows_max || n_groups > FwdGroupTab::MAX) {
-        c->err = "wide_forward_actor_groups: rows outside the context's buffers";
-        return BPPO_ERR_ARG;
-    }
-    if (any_norm) {
-        hipLaunchKernelGGL(k_obs_norm_groups, dim3((span_rows + 7) / 8), dim3(256), 0, c->stream, gbase, tab, n_groups,
-                           c->D, ldxc, xc + c->G, 10.0f);
-        TRY(launch_check(c, "k_obs_norm_groups"));
-    }
-    const float *x = xc + c->G;
-    int ldx = ldxc;
-    for (int l = 0; l < n.n_actor_hidden; l++) {
-        float *h = c->d_hbuf + c->hoff[l];
-        BPPO_HIP(c, gemm_fwd_groups(c->stream, gbase, tab, n_groups, span_r0, span_rows, n.out[l], n.in[l], x, ldx, n.w[l],
-                                    n.b[l], c->cfg.relu ? 1 : 2, h, n.out[l]));
-        x = h; ldx = n.out[l];
-    }
-    BPPO_HIP(c, gemm_fwd_groups(c->stream, gbase, tab, n_groups, span_r0, span_rows, c->A, n.in[n.policy], x, ldx,
-                                n.w[n.policy], n.b[n.policy], 0, logits, c->A));
-    return BPPO_OK;
-}
-
 // collect_rollouts (ppo.rs:213-500), self-play path; with an opponent pool
 // (opponents.hip) collect_rollouts_with_opponents (ppo.rs:537-1063).  Observation normalizer:
 // each step's obs columns normalized in place with the lagged stats (raw copy

@@ -92,8 +92,9 @@ def _seats(n_opp, P, K, seed):
 
 
 def test_liars_dice_ctde_opponents_set_twice(baseline):
-    """the second bppo_opponents_set re-sizes the model, normalizer and seat buffers (1 -> 3
-    models, 32 -> 48 opponent envs): it releases the four it replaces"""
+    """the second bppo_opponents_set re-sizes the model set's parameters and normalizers and the
+    seat buffers (1 -> 3 models, 32 -> 48 opponent envs): it releases what it replaces (the
+    set's table keeps its size)"""
     cfg = bppo.make_config("liars_dice_ctde", hidden_size=64, num_hidden=2, critic_hidden_size=64, critic_num_hidden=2,
                            normalize_obs=True, **SMALL)
     tr = bppo.Trainer(cfg)

@@ -277,12 +277,13 @@ def test_normalizers_rollout_update_second_rollout(env, N, T, ctde):
 # collect_rollouts_with_opponents (ppo.rs:537-1063) + the learner-row filter of
 # ppo_update (ppo.rs:1696-1753).  Oracle and device get the same opponent
 # models (one with its own obs normalizer), seats and current opponents.
-def _opponent_setup(cfg, tr, ot, env, n_opp, K, seed=3):
+# seated: the models the seats are drawn from (default: all K); norm_model: the one with a normalizer
+def _opponent_setup(cfg, tr, ot, env, n_opp, K, seed=3, seated=None, norm_model=None):
     kind, D, A, P, G = ENV[env]
     rng = np.random.default_rng(seed)
     params = np.stack([bppo.orthogonal_init(cfg, seed=100 + k) for k in range(K)])
     norms = [None] * K
-    norms[K - 1] = (rng.normal(size=D) * 0.1, (rng.random(D) + 0.5) * 500.0, 500.0)
+    norms[K - 1 if norm_model is None else norm_model] = (rng.normal(size=D) * 0.1, (rng.random(D) + 0.5) * 500.0, 500.0)
     lp = rng.integers(0, P, n_opp).astype(np.int32)
     po = np.full((n_opp, P), -1, np.int32)
     for e in range(n_opp):
@@ -290,6 +291,10 @@ def _opponent_setup(cfg, tr, ot, env, n_opp, K, seed=3):
             if p != lp[e]:
                 po[e, p] = rng.integers(0, K)
     co = rng.integers(0, K, P - 1).astype(np.int32)
+    if seated is not None:
+        seated = np.asarray(seated, np.int32)
+        po = np.where(po >= 0, seated[rng.integers(0, len(seated), po.shape)], -1).astype(np.int32)
+        co = seated[rng.integers(0, len(seated), P - 1)]
     tr.ctx.set_opponents(params, norms, n_opp, lp, po, co)
     ot.set_opponents(params, norms, n_opp, lp, po.reshape(-1), co)
     return P
@@ -300,11 +305,11 @@ OPP_CASES = [("connect_four", 64, 16, None, 40, 2, False), ("liars_dice", 48, 12
              ("liars_dice", 48, 10, None, 30, 2, True)]
 
 
-@pytest.mark.parametrize("env,N,T,ctde,n_opp,K,norm", OPP_CASES)
-def test_opponent_pool_rollout_update_bit_exact(env, N, T, ctde, n_opp, K, norm):
+def _opponent_pool_case(env, N, T, ctde, n_opp, K, norm, cfg_kw=None, setup_kw=None):
+    cfg_kw, setup_kw = cfg_kw or {}, setup_kw or {}
     kw = dict(normalize_obs=True, normalize_returns=True) if norm else {}
-    cfg, tr, ot = _pair(env, N, T, ctde=ctde, **kw)
-    P = _opponent_setup(cfg, tr, ot, env, n_opp, K)
+    cfg, tr, ot = _pair(env, N, T, ctde=ctde, **kw, **cfg_kw)
+    P = _opponent_setup(cfg, tr, ot, env, n_opp, K, **setup_kw)
     for rnd in range(2):
         if norm and rnd:                       # layered: the oracle's normalizer state
             kind, D, A, P_, G = ENV[env]
@@ -316,6 +321,8 @@ def test_opponent_pool_rollout_update_bit_exact(env, N, T, ctde, n_opp, K, norm)
         lp, po = tr.ctx.opponent_envs()
         olp, opo = ot.opponent_envs(n_opp, P)
         assert np.array_equal(lp, olp) and np.array_equal(po.reshape(-1), opo)
+        if "seated" in setup_kw:               # the reshuffles seat no other model: the other groups stay empty
+            assert set(po[po >= 0].tolist()) <= set(setup_kw["seated"])
         v = tr.ctx.buffer("valid").reshape(T, N)
         assert (n_opp == N or v[:, n_opp:].min() == 1.0) and 0.0 < v[:, :n_opp].mean() < 1.0
         bppo.compute_gae(tr.ctx); ot.gae()
@@ -333,3 +340,30 @@ def test_opponent_pool_rollout_update_bit_exact(env, N, T, ctde, n_opp, K, norm)
         assert_params_close(tr.model.get_params(), ot.params())
         tr.model.set_params(ot.params())
     tr.close(); ot.close()
+    return v
+
+
+@pytest.mark.parametrize("env,N,T,ctde,n_opp,K,norm", OPP_CASES)
+def test_opponent_pool_rollout_update_bit_exact(env, N, T, ctde, n_opp, K, norm):
+    _opponent_pool_case(env, N, T, ctde, n_opp, K, norm)
+
+
+# The models' forwards are one launch per layer over every model's rows (model_set.hip), in
+# row tiles of 128 per model:
+#   tile     one model with about N / 2 = 192 rows a step: a group that crosses a tile
+#   limit    K = 15 (the pool's limit) with the seats drawn from models {0, 3, 14}: twelve
+#            groups are empty every step; model 3 carries an obs normalizer (count 500)
+#   limit-ctde  the same on Liar's Dice CTDE, whose actor input sits at column G of the row
+OPP_GROUP_CASES = {
+    "tile": ("connect_four", 384, 4, None, 384, 1, dict(hidden_size=64, num_hidden=2), {}),
+    "limit": ("connect_four", 64, 8, None, 40, 15, {}, dict(seated=[0, 3, 14], norm_model=3)),
+    "limit-ctde": ("liars_dice", 64, 8, None, 40, 15, {}, dict(seated=[0, 3, 14], norm_model=3)),
+}
+
+
+@pytest.mark.parametrize("case", list(OPP_GROUP_CASES))
+def test_opponent_pool_grouped_forward_bit_exact(case):
+    env, N, T, ctde, n_opp, K, cfg_kw, setup_kw = OPP_GROUP_CASES[case]
+    v = _opponent_pool_case(env, N, T, ctde, n_opp, K, False, cfg_kw, setup_kw)
+    if case == "tile":                         # the last rollout's opponent rows per step: more than one tile
+        assert (v == 0.0).sum(axis=1).min() > 128
