@@ -280,7 +280,7 @@ static bppo_status ctx_init(bppo_ctx *c, const bppo_config *cfg, int dev, void *
     BPPO_HIP(c, c->zalloc(&c->d_fy, 4 * TN));
     BPPO_HIP(c, c->zalloc(&c->d_scan, TN / 8192 + 2));
     BPPO_HIP(c, fy_ranges_init(c->mem, c->fyr, (uint32_t)TN));
-    BPPO_HIP(c, c->zalloc(&c->d_red, 4 * 1024 + 64));
+    BPPO_HIP(c, c->zalloc(&c->d_red, RED_SCRATCH_DOUBLES));
     BPPO_HIP(c, c->zalloc(&c->d_mb_stats, (size_t)4 * std::max(cfg->num_minibatches, 2)));
     c->d_mb_cur = c->d_mb_stats;
     BPPO_HIP(c, c->zalloc(&c->d_rows, (size_t)cfg->num_epochs * cfg->num_minibatches * (WM_COUNT + 4)));

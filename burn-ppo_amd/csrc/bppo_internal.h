@@ -61,6 +61,10 @@ constexpr int ROLL_TAIL_OFF = ROLL_NTAIL_OFF + 1;
 constexpr int ROLL_HOST_WORDS = ROLL_TAIL_OFF + BPPO_EPISODE_TAIL * (int)(sizeof(bppo_episode_tail) / 8);
 static_assert(sizeof(bppo_episode_stats) % 8 == 0 && sizeof(bppo_episode_tail) % 8 == 0, "slot layout in doubles");
 constexpr int ADV_STREAM_BLOCKS = 512, ADV_STREAM_MAXM = 16;   // k_adv_stream grid, most minibatches
+// doubles in the reduction scratch d_red: k_ev's 4 x 1024 block sums, k_adv_epoch's 8 per
+// block and one sum of squares per ADAM_CHUNK block of the Adam step (k_update.hip); the
+// launchers that write more than a fixed count check their block count against it
+constexpr int RED_SCRATCH_DOUBLES = 4 * 1024 + 64;
 // metric slots after the gradient, d_grad[np + k]: GRAD_METRIC_SLOTS (= WM_COUNT, bppo_wide.h)
 // travel with the gradient through the W > 1 SUM all-reduce; value_error_max (slot
 // GRAD_VEMAX) cannot be summed, so its reduction also writes a rank-local copy to slot
@@ -665,6 +669,22 @@ inline double schedule_get(const std::vector<double> &v, const std::vector<uint6
             return v[i] + (v[i + 1] - v[i]) * t;
         }
     return v[n - 1];
+}
+// Adam's bias corrections 1 - beta^step as burn-optim computes them: f32 powers by squaring
+inline float powi_f32(float a, int b) {   // compiler-rt __powisf2 (Rust f32::powi)
+    int recip = b < 0;
+    float r = 1.0f;
+    for (;;) {
+        if (b & 1) r *= a;
+        b /= 2;
+        if (b == 0) break;
+        a *= a;
+    }
+    return recip ? 1.0f / r : r;
+}
+inline void adam_bias_corrections(int step, float *c1, float *c2) {
+    *c1 = 1.0f - powi_f32(0.9f, step);
+    *c2 = 1.0f - powi_f32(0.999f, step);
 }
 // the shaping bonus the envs add this step: reward_shaping_coef.get(current_step) as f32
 inline float shaping_coef(const bppo_ctx *c) { return (float)schedule_get(c->shaping_v, c->shaping_s, c->env_step); }

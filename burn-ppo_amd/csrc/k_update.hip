@@ -15,6 +15,7 @@
 namespace bppo {
 
 constexpr int STAT_BLOCKS = 1024;   // partial blocks of the explained-variance sums
+static_assert(4 * STAT_BLOCKS <= RED_SCRATCH_DOUBLES, "k_ev's block sums fit the reduction scratch");
 
 // =========================================================== fwd + bwd ====
 // metric slots appended after the parameters in the gradient slab
@@ -1470,6 +1471,13 @@ __global__ void __launch_bounds__(SLAB1_COLS * SLAB_GROUPS) k_slab_reduce1(const
         if (is_max) *vemax_local = (float)s;     // kept out of the W > 1 SUM all-reduce
     }
 }
+// the launch on plain device pointers: slab [rows][width], grad [width]; the caller reads
+// the launch status (hipGetLastError)
+static void launch_slab_reduce_raw(const float *slab, int rows, int width, float *grad, float *vemax_local,
+                                   hipStream_t s) {
+    hipLaunchKernelGGL(k_slab_reduce1, dim3((width + SLAB1_COLS - 1) / SLAB1_COLS), dim3(SLAB1_COLS * SLAB_GROUPS), 0, s,
+                       slab, rows, width, grad, vemax_local);
+}
 
 // per-tensor norm clip + Adam (burn-optim 0.20 restated).  Each tensor is cut
 // into ADAM_CHUNK-element blocks: pass 1 writes every block's sum of squares,
@@ -1605,8 +1613,9 @@ __global__ void __launch_bounds__(256) k_ev(size_t n, const float *val, const fl
 // utils.rs:80-89): f64 sum and sum of squares, min, max over each minibatch's
 // shuffled rows.  Block b owns positions [b C, (b + 1) C) (EpochSplit in
 // bppo_internal.h); the final pass adds the block partials of each minibatch in
-// block order (deterministic).  On the ranged shuffle path the partials come
-// from the fused Fisher-Yates final pass (k_shuffle.hip k_fy_final_ranged).
+// block order (deterministic).  This is the path of an update that has no inverse
+// permutation (the opponent pool's mapped permutation), of more than ADV_STREAM_MAXM
+// minibatches and of B < M; every other update takes k_adv_stream below.
 // 1024 threads per block, ADV_U positions per thread in flight (perm then adv are
 // two dependent random-ish loads; one pair at a time left the block latency bound)
 constexpr int ADV_THREADS = 1024, ADV_U = 4;
@@ -1780,30 +1789,68 @@ __global__ void __launch_bounds__(256) k_adv_stream_final(const double *part, in
     stats[m * 4 + 3] = (float)smx[0];
 }
 
-bppo_status launch_epoch_adv_stats(bppo_ctx *c, uint32_t B, int M, const uint32_t *inv) {
-    const EpochSplit sp{B, B / (uint32_t)M, B % (uint32_t)M, (uint32_t)M};
-    if (inv && M <= ADV_STREAM_MAXM && sp.base > 0) {
+// which kernels one epoch's statistics take and their block chunking: path 0 = k_adv_epoch
+// over the permutation, 4 / 8 / 16 = k_adv_stream<path> over its inverse
+struct AdvPlan { int path; uint32_t C, nblk; };
+static AdvPlan adv_plan(uint32_t B, int M, bool have_inv) {
+    const uint32_t base = B / (uint32_t)M;
+    if (have_inv && M <= ADV_STREAM_MAXM && base > 0) {
         const uint32_t C = (B + ADV_STREAM_BLOCKS - 1) / ADV_STREAM_BLOCKS;
-        const int nblk = (int)((B + C - 1) / C);
-        const int MB = M <= 4 ? 4 : (M <= 8 ? 8 : 16);
-        if (MB == 4) hipLaunchKernelGGL(k_adv_stream<4>, dim3(nblk), dim3(256), 0, c->stream, c->d_adv, inv, sp, C, c->d_advpart);
-        else if (MB == 8) hipLaunchKernelGGL(k_adv_stream<8>, dim3(nblk), dim3(256), 0, c->stream, c->d_adv, inv, sp, C, c->d_advpart);
-        else hipLaunchKernelGGL(k_adv_stream<16>, dim3(nblk), dim3(256), 0, c->stream, c->d_adv, inv, sp, C, c->d_advpart);
-        hipLaunchKernelGGL(k_adv_stream_final, dim3(M), dim3(256), 0, c->stream, c->d_advpart, nblk, MB, sp, c->d_mb_stats);
-        TRY(launch_check(c, __func__));
-        return BPPO_OK;
+        return AdvPlan{M <= 4 ? 4 : (M <= 8 ? 8 : 16), C, (B + C - 1) / C};
     }
     uint32_t C = (B + 511) / 512;
-    if (sp.base > 0 && C > sp.base) C = sp.base;
-    if (sp.base == 0) C = 1;
-    const uint32_t nblk = (B + C - 1) / C;
-    if ((size_t)nblk * 8 > 4 * 1024 + 64) { c->err = "epoch advantage stats: too many minibatches"; return BPPO_ERR_UNSUPPORTED; }
-    hipLaunchKernelGGL(k_adv_epoch, dim3(nblk), dim3(ADV_THREADS), 0, c->stream, c->d_adv, c->d_perm, sp, C, c->d_red);
-    hipLaunchKernelGGL(k_adv_epoch_final, dim3(M), dim3(256), 0, c->stream, c->d_red, (int)nblk, C, sp, c->d_mb_stats);
-    TRY(launch_check(c, __func__));
-    return BPPO_OK;
+    if (base > 0 && C > base) C = base;
+    if (base == 0) C = 1;
+    return AdvPlan{0, C, (B + C - 1) / C};
+}
+// k_adv_epoch writes 8 doubles per block into the reduction scratch
+static bool adv_plan_fits(const AdvPlan &p) { return p.path != 0 || (size_t)p.nblk * 8 <= (size_t)RED_SCRATCH_DOUBLES; }
+
+// the launches on plain device pointers.  red holds RED_SCRATCH_DOUBLES doubles, advpart
+// ADV_STREAM_BLOCKS * ADV_STREAM_MAXM * 4, stats M * 4 floats; inv == nullptr takes the
+// permutation path.  *path_out (may be null) = the plan's path
+static bppo_status launch_epoch_adv_stats_raw(uint32_t B, int M, const float *adv, const uint32_t *perm,
+                                              const uint32_t *inv, double *red, double *advpart, float *stats,
+                                              hipStream_t s, int *path_out, hipError_t *herr) {
+    const EpochSplit sp{B, B / (uint32_t)M, B % (uint32_t)M, (uint32_t)M};
+    const AdvPlan p = adv_plan(B, M, inv != nullptr);
+    if (path_out) *path_out = p.path;
+    if (herr) *herr = hipSuccess;
+    if (!adv_plan_fits(p)) return BPPO_ERR_UNSUPPORTED;
+    const uint32_t C = p.C;
+    const int nblk = (int)p.nblk;
+    if (p.path) {
+        const int MB = p.path;
+        if (MB == 4) hipLaunchKernelGGL(k_adv_stream<4>, dim3(nblk), dim3(256), 0, s, adv, inv, sp, C, advpart);
+        else if (MB == 8) hipLaunchKernelGGL(k_adv_stream<8>, dim3(nblk), dim3(256), 0, s, adv, inv, sp, C, advpart);
+        else hipLaunchKernelGGL(k_adv_stream<16>, dim3(nblk), dim3(256), 0, s, adv, inv, sp, C, advpart);
+        hipLaunchKernelGGL(k_adv_stream_final, dim3(M), dim3(256), 0, s, advpart, nblk, MB, sp, stats);
+    } else {
+        hipLaunchKernelGGL(k_adv_epoch, dim3(nblk), dim3(ADV_THREADS), 0, s, adv, perm, sp, C, red);
+        hipLaunchKernelGGL(k_adv_epoch_final, dim3(M), dim3(256), 0, s, red, nblk, C, sp, stats);
+    }
+    const hipError_t e = hipGetLastError();
+    if (herr) *herr = e;
+    return e == hipSuccess ? BPPO_OK : BPPO_ERR_HIP;
 }
 
+bppo_status launch_epoch_adv_stats(bppo_ctx *c, uint32_t B, int M, const uint32_t *inv) {
+    hipError_t e = hipSuccess;
+    const bppo_status st = launch_epoch_adv_stats_raw(B, M, c->d_adv, c->d_perm, inv, c->d_red, c->d_advpart,
+                                                      c->d_mb_stats, c->stream, nullptr, &e);
+    if (st == BPPO_ERR_UNSUPPORTED) c->err = "epoch advantage stats: too many minibatches";
+    if (st == BPPO_ERR_HIP) return hip_fail(c, e, __func__);
+    return st;
+}
+
+// the block table of a filled tensor table: tensor t owns blocks [blk0[t], blk0[t + 1])
+// of ADAM_CHUNK elements; -> the block count (64-bit: the caller checks it before use)
+static int64_t adam_blocks(AdamArgs &a) {
+    int64_t nb = 0;
+    for (int t = 0; t < a.nt; t++) { a.blk0[t] = (int)nb; nb += ((int64_t)a.t[t].len + ADAM_CHUNK - 1) / ADAM_CHUNK; }
+    a.blk0[a.nt] = (int)nb;
+    return nb;
+}
 static AdamArgs adam_args(bppo_ctx *c, float lr, const float *c1, const float *c2) {
     AdamArgs a;
     a.params = c->d_params; a.grad = c->d_grad; a.m1 = c->d_m1; a.m2 = c->d_m2;
@@ -1815,9 +1862,7 @@ static AdamArgs adam_args(bppo_ctx *c, float lr, const float *c1, const float *c
     a.lr = lr; a.max_norm = (float)c->cfg.max_grad_norm; a.eps = (float)c->cfg.adam_epsilon;
     a.inv_world = 1.0f / (float)c->world;
     a.part = c->d_red;
-    int nb = 0;
-    for (int t = 0; t < a.nt; t++) { a.blk0[t] = nb; nb += (a.t[t].len + ADAM_CHUNK - 1) / ADAM_CHUNK; }
-    a.blk0[a.nt] = nb;
+    adam_blocks(a);
     return a;
 }
 
@@ -1914,9 +1959,8 @@ bppo_status launch_minibatch(bppo_ctx *c, uint32_t start, uint32_t n, float ent_
     TRY(launch_check(c, __func__));
     const int width = (int)c->net.n_params + NUM_M;
     static_assert(M_VEMAX == GRAD_VEMAX && NUM_M <= GRAD_METRIC_SLOTS, "metric slot layout");
-    hipLaunchKernelGGL(k_slab_reduce1, dim3((width + SLAB1_COLS - 1) / SLAB1_COLS), dim3(SLAB1_COLS * SLAB_GROUPS), 0,
-                       c->stream, c->d_slab,
-                       c->slab_used, width, c->d_grad, c->d_grad + c->net.n_params + GRAD_VEMAX_LOCAL);
+    launch_slab_reduce_raw(c->d_slab, c->slab_used, width, c->d_grad, c->d_grad + c->net.n_params + GRAD_VEMAX_LOCAL,
+                           c->stream);
     TRY(launch_check(c, __func__));
     return BPPO_OK;
 }
@@ -1934,20 +1978,38 @@ bppo_status launch_metric_row(bppo_ctx *c, float *dst, int nm) {
     return BPPO_OK;
 }
 
+// clip + Adam of a filled table (adam_blocks done) on plain device pointers.  fused: k_adam1,
+// which also copies the metric row (every tensor within one ADAM_CHUNK: BPPO_ERR_ARG
+// otherwise); else k_adam_norm + k_adam, then k_metric_row when metric_dst is given.
+// BPPO_ERR_UNSUPPORTED before any launch when the table has more blocks than a.part
+// (RED_SCRATCH_DOUBLES doubles) holds partials
+static bppo_status launch_adam_raw(const AdamArgs &a, bool fused, const float *gtail, const float *mb_stats, int nm,
+                                   float *metric_dst, hipStream_t s, hipError_t *herr) {
+    const int nb = a.blk0[a.nt];
+    if (herr) *herr = hipSuccess;
+    if (nb > RED_SCRATCH_DOUBLES) return BPPO_ERR_UNSUPPORTED;
+    if (fused) {
+        if (nb != a.nt) return BPPO_ERR_ARG;
+        hipLaunchKernelGGL(k_adam1, dim3(nb), dim3(ADAM1_THREADS), 0, s, a, gtail, mb_stats, nm, metric_dst);
+    } else {
+        hipLaunchKernelGGL(k_adam_norm, dim3(nb), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_adam, dim3(nb), dim3(256), 0, s, a);
+        if (metric_dst) hipLaunchKernelGGL(k_metric_row, dim3(1), dim3(64), 0, s, gtail, mb_stats, nm, metric_dst);
+    }
+    const hipError_t e = hipGetLastError();
+    if (herr) *herr = e;
+    return e == hipSuccess ? BPPO_OK : BPPO_ERR_HIP;
+}
+
 bppo_status launch_adam(bppo_ctx *c, float lr, const float *c1, const float *c2, float *metric_dst, int nm) {
     const AdamArgs a = adam_args(c, lr, c1, c2);
-    const int nb = a.blk0[a.nt];
-    if (nb == a.nt && metric_dst) {       // one chunk per tensor: fused
-        hipLaunchKernelGGL(k_adam1, dim3(nb), dim3(ADAM1_THREADS), 0, c->stream, a, c->d_grad + c->net.n_params,
-                           c->d_mb_cur, nm, metric_dst);
-        TRY(launch_check(c, __func__));
-        return BPPO_OK;
-    }
-    hipLaunchKernelGGL(k_adam_norm, dim3(nb), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(k_adam, dim3(nb), dim3(256), 0, c->stream, a);
-    TRY(launch_check(c, __func__));
-    if (metric_dst) return launch_metric_row(c, metric_dst, nm);
-    return BPPO_OK;
+    hipError_t e = hipSuccess;
+    const bool fused = a.blk0[a.nt] == a.nt && metric_dst;       // one chunk per tensor: fused
+    const bppo_status st =
+        launch_adam_raw(a, fused, c->d_grad + c->net.n_params, c->d_mb_cur, nm, metric_dst, c->stream, &e);
+    if (st == BPPO_ERR_UNSUPPORTED) c->err = "clip + Adam: more tensor blocks than the reduction scratch holds";
+    if (st == BPPO_ERR_HIP) return hip_fail(c, e, __func__);
+    return st;
 }
 
 // enqueue: block sums into pinned h_red; explained_variance_sums reads them once the
@@ -1967,3 +2029,109 @@ void explained_variance_sums(bppo_ctx *c, double *out4) {
 }
 
 }  // namespace bppo
+
+// ----------------------------------------------------------- parity hooks ---
+// host buffers in/out, no context: the update's small kernels with the launchers' own
+// geometry on temporaries of their own (include/bppo.h)
+namespace {
+template <class T> bool up(bppo::DeviceMem &mem, T **d, const T *h, size_t n) {
+    return mem.alloc(d, n) == hipSuccess && hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+}
+template <class T> bool down(T *h, const T *d, size_t n) {
+    return hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
+}
+}  // namespace
+
+extern "C" bppo_status bppo_debug_adv_stats(uint32_t B, int32_t M, const float *adv, const uint32_t *perm,
+                                            const uint32_t *inv, float *stats, int32_t *path_out) {
+    using namespace bppo;
+    if (B < 1 || M < 1 || !adv || !perm || !stats || !path_out) return BPPO_ERR_ARG;
+    for (uint32_t i = 0; i < B; i++)
+        if (perm[i] >= B || (inv && inv[i] >= B)) return BPPO_ERR_ARG;
+    const AdvPlan plan = adv_plan(B, M, inv != nullptr);
+    if (!adv_plan_fits(plan)) return BPPO_ERR_UNSUPPORTED;
+    float *d_adv = nullptr, *d_stats = nullptr;
+    uint32_t *d_perm = nullptr, *d_inv = nullptr;
+    double *d_red = nullptr, *d_part = nullptr;
+    bppo_status s = BPPO_ERR_HIP;
+    DeviceMem mem;
+    do {
+        if (!up(mem, &d_adv, adv, B) || !up(mem, &d_perm, perm, B)) break;
+        if (inv && !up(mem, &d_inv, inv, B)) break;
+        if (mem.alloc(&d_red, RED_SCRATCH_DOUBLES) != hipSuccess) break;
+        if (mem.alloc(&d_part, (size_t)ADV_STREAM_BLOCKS * ADV_STREAM_MAXM * 4) != hipSuccess) break;
+        if (mem.alloc(&d_stats, (size_t)M * 4) != hipSuccess) break;
+        int path = -1;
+        s = launch_epoch_adv_stats_raw(B, M, d_adv, d_perm, d_inv, d_red, d_part, d_stats, nullptr, &path, nullptr);
+        if (s != BPPO_OK) break;
+        s = BPPO_ERR_HIP;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        if (!down(stats, d_stats, (size_t)M * 4)) break;
+        *path_out = path;
+        s = BPPO_OK;
+    } while (0);
+    return s;
+}
+
+extern "C" bppo_status bppo_debug_slab_reduce(int32_t rows, int32_t width, const float *slab, float *grad_out,
+                                              float *vemax_local_out) {
+    using namespace bppo;
+    if (rows < 1 || width < NUM_M || !slab || !grad_out || !vemax_local_out) return BPPO_ERR_ARG;
+    float *d_slab = nullptr, *d_grad = nullptr, *d_vemax = nullptr;
+    bppo_status s = BPPO_ERR_HIP;
+    DeviceMem mem;
+    // the guard region behind the output: grad_out [width + SLAB_GUARD], uploaded and read back whole
+    constexpr int SLAB_GUARD = 64;
+    do {
+        if (!up(mem, &d_slab, slab, (size_t)rows * width)) break;
+        if (!up(mem, &d_grad, (const float *)grad_out, (size_t)width + SLAB_GUARD)) break;
+        if (!up(mem, &d_vemax, (const float *)vemax_local_out, 1)) break;
+        launch_slab_reduce_raw(d_slab, rows, width, d_grad, d_vemax, nullptr);
+        if (hipGetLastError() != hipSuccess) break;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        if (!down(grad_out, d_grad, (size_t)width + SLAB_GUARD) || !down(vemax_local_out, d_vemax, 1)) break;
+        s = BPPO_OK;
+    } while (0);
+    return s;
+}
+
+extern "C" bppo_status bppo_debug_adam(int32_t nt, const int32_t *lens, int32_t step, int32_t world, float lr,
+                                       float max_norm, float eps, int32_t fused, const float *grad, float *params,
+                                       float *m1, float *m2, const float *gtail, const float *mb_stats, int32_t nm,
+                                       float *metric_row_out) {
+    using namespace bppo;
+    if (nt < 1 || nt > 32 || !lens || step < 1 || world < 1 || (fused != 0 && fused != 1)) return BPPO_ERR_ARG;
+    if (!grad || !params || !m1 || !m2 || !gtail || !mb_stats || !metric_row_out) return BPPO_ERR_ARG;
+    if (nm < 0 || nm > GRAD_METRIC_SLOTS) return BPPO_ERR_ARG;
+    AdamArgs a;
+    a.nt = nt;
+    int64_t np = 0;
+    float c1, c2;
+    adam_bias_corrections(step, &c1, &c2);
+    for (int t = 0; t < nt; t++) {
+        if (lens[t] < 1 || np + lens[t] > INT32_MAX) return BPPO_ERR_ARG;
+        if (fused && lens[t] > ADAM_CHUNK) return BPPO_ERR_ARG;
+        a.t[t] = AdamTensor{(int)np, lens[t], c1, c2};
+        np += lens[t];
+    }
+    if (adam_blocks(a) > RED_SCRATCH_DOUBLES) return BPPO_ERR_UNSUPPORTED;
+    a.lr = lr; a.max_norm = max_norm; a.eps = eps; a.inv_world = 1.0f / (float)world;
+    float *d_gtail = nullptr, *d_stats = nullptr, *d_row = nullptr;
+    bppo_status s = BPPO_ERR_HIP;
+    DeviceMem mem;
+    do {
+        if (!up(mem, &a.grad, grad, (size_t)np) || !up(mem, &a.params, (const float *)params, (size_t)np)) break;
+        if (!up(mem, &a.m1, (const float *)m1, (size_t)np) || !up(mem, &a.m2, (const float *)m2, (size_t)np)) break;
+        if (!up(mem, &d_gtail, gtail, (size_t)GRAD_METRIC_SLOTS + 1) || !up(mem, &d_stats, mb_stats, 4)) break;
+        if (!up(mem, &d_row, (const float *)metric_row_out, (size_t)nm + 4)) break;
+        if (mem.alloc(&a.part, RED_SCRATCH_DOUBLES) != hipSuccess) break;
+        s = launch_adam_raw(a, fused != 0, d_gtail, d_stats, nm, d_row, nullptr, nullptr);
+        if (s != BPPO_OK) break;
+        s = BPPO_ERR_HIP;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+        if (!down(params, a.params, (size_t)np) || !down(m1, a.m1, (size_t)np) || !down(m2, a.m2, (size_t)np)) break;
+        if (!down(metric_row_out, d_row, (size_t)nm + 4)) break;
+        s = BPPO_OK;
+    } while (0);
+    return s;
+}

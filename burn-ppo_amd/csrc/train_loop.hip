@@ -30,18 +30,6 @@ static double tsc_per_ms() {
     return v;
 }
 
-static float powi_f32(float a, int b) {   // compiler-rt __powisf2 (Rust f32::powi)
-    int recip = b < 0;
-    float r = 1.0f;
-    for (;;) {
-        if (b & 1) r *= a;
-        b /= 2;
-        if (b == 0) break;
-        a *= a;
-    }
-    return recip ? 1.0f / r : r;
-}
-
 // wait for an event of the context stream: the host thread sleeps instead of polling
 // (see sync_stream, bppo_api.hip).
 // The per-update wait of bppo_train_steps (~12 ms on CfgB) repeats from one update to
@@ -452,8 +440,7 @@ static bppo_status minibatch_slot(bppo_ctx *c, UpdateRun &u, int ep, int mb, siz
     float c1[64], c2[64];
     for (int t = 0; t < 2 * c->net.n_layers; t++) {
         int ti = ++c->adam_t[t];
-        c1[t] = 1.0f - powi_f32(0.9f, ti);
-        c2[t] = 1.0f - powi_f32(0.999f, ti);
+        adam_bias_corrections(ti, &c1[t], &c2[t]);
     }
     float *metric_dst = c->d_rows + (size_t)u.nrow * WM_ROW;
     if (sz && c->dbg_params && u.nrow < c->dbg_params_max)   // parity hook: this minibatch's parameters

@@ -739,6 +739,39 @@ bppo_status bppo_debug_return_norm(int32_t T, int32_t N, int32_t P, double gamma
                                    const int32_t *players /*[T,N] or NULL*/, const float *valid /*[T,N] or NULL*/,
                                    double *returns_state /*[N,P] in/out*/, double *stats3 /*in/out*/,
                                    float *rew /*[T,N] out*/, float *all_rewards /*[T,N,P] in/out or NULL*/);
+/* Parity hooks of the update's small kernels (host buffers, no context).  Each checks its
+ * arguments before any HIP call.
+ *
+ * bppo_debug_adv_stats: the per-minibatch advantage statistics of one epoch, exactly the launches
+ * of the update (its own choice of kernels and block chunking).  adv [B], perm [B] the shuffled
+ * row indices, inv [B] its inverse (row -> shuffled position) or NULL, M minibatches (minibatch m
+ * holds B / M + (m < B % M) consecutive shuffled positions); stats [M][4] = mean, std, min, max.
+ * *path_out = 0 when the kernels over perm ran (inv NULL, M > 16 or B < M), else 4, 8 or 16, the
+ * bin count of the kernels over inv.  BPPO_ERR_ARG: B < 1, M < 1, a NULL adv / perm / stats /
+ * path_out, an index >= B in perm or inv; BPPO_ERR_UNSUPPORTED: more minibatches than the
+ * reduction scratch holds block partials for. */
+bppo_status bppo_debug_adv_stats(uint32_t B, int32_t M, const float *adv, const uint32_t *perm, const uint32_t *inv,
+                                 float *stats, int32_t *path_out);
+/* bppo_debug_slab_reduce: the fixed-order reduction of the minibatch kernels' partial gradient
+ * rows, slab [rows][width] -> grad_out [width]: column sums, but the maximum in column
+ * width - 11 + 9 (value_error_max of the 11 metric slots behind the parameters), which also goes
+ * to *vemax_local_out.  grad_out holds width + 64 floats, uploaded before and read back after the
+ * launch whole, so the caller sees whatever was written behind column width - 1.
+ * BPPO_ERR_ARG: rows < 1, width < 11, a NULL pointer. */
+bppo_status bppo_debug_slab_reduce(int32_t rows, int32_t width, const float *slab, float *grad_out,
+                                   float *vemax_local_out);
+/* bppo_debug_adam: per-tensor norm clip + Adam step `step` (>= 1: the bias corrections are the
+ * update's f32 powers) of nt tensors laid out back to back (tensor t at the running sum of lens),
+ * the gradient scaled by 1 / world first.  fused = 1: the one-launch kernel for tables whose
+ * tensors all fit one 4096-element block; fused = 0: the norm pass, the update pass and the metric
+ * row kernel.  params, m1, m2 in/out.  metric_row_out [nm + 4] = gtail [0, nm) with slot 9 read
+ * from gtail[14] (the rank-local value_error_max), then mb_stats [4]; gtail holds 15 floats.
+ * BPPO_ERR_ARG: nt outside 1..32, a len < 1, step or world < 1, fused not 0 / 1, nm outside
+ * 0..14, a NULL pointer, fused = 1 with a len > 4096; BPPO_ERR_UNSUPPORTED: more 4096-element
+ * blocks than the reduction scratch holds partials for (4160). */
+bppo_status bppo_debug_adam(int32_t nt, const int32_t *lens, int32_t step, int32_t world, float lr, float max_norm,
+                            float eps, int32_t fused, const float *grad, float *params, float *m1, float *m2,
+                            const float *gtail, const float *mb_stats, int32_t nm, float *metric_row_out);
 /* Parity hook of the evaluation loop's forward (host buffers): the actor logits of n_models
  * models' row groups.  Model k owns rows [gbase[k], gbase[k + 1]) of xc [gbase[n_models]][G + D]
  * ([priv | obs] rows, raw: a model's obs normalizer is applied as the loop applies it) and of

@@ -180,6 +180,58 @@ def test_debug_return_norm_rejects_bad_arguments_before_any_hip_call(so):
         assert call(**bad) == L.ERR_ARG, bad
 
 
+def test_debug_update_kernel_hooks_reject_bad_arguments_before_any_hip_call(so):
+    """bppo_debug_adv_stats, bppo_debug_slab_reduce and bppo_debug_adam check their sizes, their
+    required pointers and the reduction scratch's capacity before the first HIP call, so
+    BPPO_ERR_ARG / BPPO_ERR_UNSUPPORTED come back without a GPU."""
+    import numpy as np
+    import bppo._lib as L
+    lib = L.lib()
+    ptr = lambda a: None if a is None else a.ctypes.data
+
+    B, M = 8, 2
+    adv = np.zeros(B, np.float32); perm = np.arange(B, dtype=np.uint32); stats = np.zeros((M, 4), np.float32)
+    path = C.c_int32(-1)
+
+    def adv_call(B=B, M=M, adv=adv, perm=perm, inv=perm, stats=stats, path=C.byref(path)):
+        return lib.bppo_debug_adv_stats(B, M, ptr(adv), ptr(perm), ptr(inv), ptr(stats), path)
+
+    out_of_range = perm.copy(); out_of_range[3] = B
+    for bad in (dict(B=0), dict(M=0), dict(M=-1), dict(adv=None), dict(perm=None), dict(stats=None), dict(path=None),
+                dict(perm=out_of_range), dict(inv=out_of_range)):
+        assert adv_call(**bad) == L.ERR_ARG, bad
+    # one row per block over the permutation (B < M): 600 blocks of 8 partials exceed the scratch
+    big = np.arange(600, dtype=np.uint32)
+    assert adv_call(B=600, M=601, adv=np.zeros(600, np.float32), perm=big, inv=None,
+                    stats=np.zeros((601, 4), np.float32)) == L.ERR_UNSUPPORTED
+
+    slab = np.zeros((2, 16), np.float32); grad = np.zeros(16 + 64, np.float32); vm = np.zeros(1, np.float32)
+
+    def slab_call(rows=2, width=16, slab=slab, grad=grad, vm=vm):
+        return lib.bppo_debug_slab_reduce(rows, width, ptr(slab), ptr(grad), ptr(vm))
+
+    for bad in (dict(rows=0), dict(rows=-1), dict(width=10), dict(width=0), dict(slab=None), dict(grad=None),
+                dict(vm=None)):
+        assert slab_call(**bad) == L.ERR_ARG, bad
+
+    lens = np.array([4, 2], np.int32); f = np.zeros(6, np.float32)
+    tail = np.zeros(15, np.float32); st4 = np.zeros(4, np.float32); row = np.zeros(18, np.float32)
+
+    def adam_call(nt=2, lens=lens, step=1, world=1, fused=0, grad=f, params=f, m1=f, m2=f, tail=tail, st4=st4, nm=14,
+                  row=row):
+        return lib.bppo_debug_adam(nt, ptr(lens), step, world, 1e-3, 0.5, 1e-5, fused, ptr(grad), ptr(params), ptr(m1),
+                                   ptr(m2), ptr(tail), ptr(st4), nm, ptr(row))
+
+    for bad in (dict(nt=0), dict(nt=-1), dict(nt=33), dict(lens=None), dict(lens=np.array([4, 0], np.int32)),
+                dict(step=0), dict(world=0), dict(fused=2), dict(grad=None), dict(params=None), dict(m1=None),
+                dict(m2=None), dict(tail=None), dict(st4=None), dict(row=None), dict(nm=-1), dict(nm=15),
+                dict(fused=1, lens=np.array([4097, 2], np.int32))):      # fused: every tensor within one chunk
+        assert adam_call(**bad) == L.ERR_ARG, bad
+    # 32 tensors of 131 chunks each: 4192 block partials, the scratch holds 4160 -- refused before
+    # any buffer is read (the arrays above are far smaller than the table)
+    assert adam_call(nt=32, lens=np.full(32, 131 * 4096, np.int32)) == L.ERR_UNSUPPORTED
+
+
 def test_null_context_is_an_argument_error(so):
     """every setter checks its context before touching it (bppo_optimizer_set
     dereferenced a NULL ctx); no HIP call is made, so this runs without a GPU."""

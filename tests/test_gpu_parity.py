@@ -230,6 +230,57 @@ def test_update_matches_oracle_and_rng_chain_exact():
     tr.close(); ot.close()
 
 
+@pytest.mark.parametrize("M", [3, 12, 16, 17])
+def test_update_ragged_splits_match_oracle_row_by_row(M):
+    """B = 1000 rows in M minibatches: ragged splits (1000 % M != 0) on k_adv_stream<4> (M = 3),
+    k_adv_stream<16> (12 and 16, every bin in use) and the permutation path (17).  Besides the
+    update's metrics, parameters and RNG position, every minibatch's row against the oracle's
+    log, and its four advantage statistics against exact arithmetic on the minibatch's rows, by
+    the bars of tests/test_gpu_update_kernels.py."""
+    import update_kernels_ref as R
+    from parity_util import summand_magnitude
+    N, T, E, TOL = 50, 20, 2, 1e-5
+    B = N * T
+    cfg, tr, ot = _pair(N, T, num_minibatches=M, num_epochs=E)
+    try:
+        bppo.collect_rollouts(tr.ctx); ot.collect()
+        bppo.compute_gae(tr.ctx); ot.gae()
+        adv = ot.buffer("advantages")
+        tr.ctx.set_buffer("advantages", adv)
+        tr.ctx.set_buffer("returns", ot.buffer("returns"))
+        m = bppo.ppo_update(tr.ctx, 1e-3, 0.01)
+        om = ot.update()
+        assert tr.ctx.rng_pos() == ot.rng_pos()
+        assert_metrics_close(m, om, values=ot.buffer("values"), returns=ot.buffer("returns"), advantages=adv)
+        assert_params_close(tr.model.get_params(), ot.params())
+        rows, log = tr.ctx.minibatch_rows(), ot.minibatch_log()
+        assert len(rows) == len(log) == E * M
+        perms = [tr.ctx.buffer(f"perm_ep:{e}", np.uint32) for e in range(E)]
+        bounds = R.mb_bounds(B, M)
+        pl_mag = summand_magnitude(adv)
+        n_frag, worst = 0, 0.0
+        for k, (r, o) in enumerate(zip(rows, log)):
+            e, mb = divmod(k, M)
+            s, end = bounds[mb]
+            n = float(r[10])
+            assert n == end - s, (k, n)
+            dev = {"policy_loss": r[0] / n, "value_loss": 0.5 * r[1] / n, "entropy": r[2] / n, "approx_kl": r[3] / n,
+                   "clip_fraction": r[4] / n, "value_mean": r[5] / n, "returns_mean": r[6] / n,
+                   "value_error_mean": r[7] / n, "value_error_max": r[9]}
+            floors = {"policy_loss": pl_mag, "clip_fraction": 1.0 / n}
+            absf = {"approx_kl": 2.0 ** -24 / np.sqrt(n)}
+            for f in dev:
+                bar = max(TOL * max(abs(o[f]), floors.get(f, 0.0)), absf.get(f, 0.0), 1e-37)
+                assert abs(dev[f] - o[f]) <= bar, (k, f, dev[f], o[f])
+            frag, ratio = R.check_adv_stats(r[14:18], R.rows_reference(adv[perms[e][s:end]]), ("minibatch", k))
+            n_frag += frag
+            worst = max(worst, ratio)
+        print(f"\nM={M}: fragile means {n_frag} of {E * M}, worst std error / bound {worst:.3g}")
+        assert n_frag <= R.fragile_cap(E * M)
+    finally:
+        tr.close(); ot.close()
+
+
 def test_shuffle_permutation_bit_exact():
     N, T = 50, 20
     cfg, tr, ot = _pair(N, T, num_minibatches=3, num_epochs=1)
