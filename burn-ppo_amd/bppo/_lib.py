@@ -140,7 +140,7 @@ EXPORTS = (
     "bppo_gae_mp_device", "bppo_last_kernel_ms", "bppo_debug_libm", "bppo_debug_shuffle_chain", "bppo_debug_chain_walk2", "bppo_minibatch_rows",
     "bppo_debug_fisher_yates", "bppo_debug_gemm", "bppo_debug_return_norm", "bppo_debug_shuffle_engine", "bppo_debug_sample",
     "bppo_debug_device_memory", "bppo_debug_fold_metrics",
-    "bppo_debug_adv_stats", "bppo_debug_slab_reduce", "bppo_debug_adam",
+    "bppo_debug_adv_stats", "bppo_debug_slab_reduce", "bppo_debug_adam", "bppo_debug_wide_loss",
     "bppo_rng_fill_bytes", "bppo_rng_from_seed", "bppo_rng_key_get", "bppo_num_param_tensors",
     "bppo_optimizer_get", "bppo_optimizer_set", "bppo_popart_get", "bppo_popart_set",
     "bppo_config_size", "bppo_update_metrics_size", "bppo_episode_size", "bppo_rollout_info_size",
@@ -244,6 +244,8 @@ def lib():
         "bppo_debug_slab_reduce": (i32, [i32, i32, vp, vp, vp]),
         "bppo_debug_adam": (i32, [i32, vp, i32, i32, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp, vp,
                                   i32, vp]),
+        "bppo_debug_wide_loss": (i32, [i32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                       vp, vp, C.c_double, C.c_double, C.c_double, i32, vp, vp]),
         "bppo_debug_shuffle_engine": (i32, [u64, u64, u64, C.c_uint32, i32, u64, i32, i32, vp, vp, vp]),
         "bppo_debug_sample": (i32, [i32, i32, vp, vp, u64, u64, u64, vp, vp]),
         "bppo_debug_device_memory": (i32, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -1,6 +1,7 @@
 // bppo_wide.h — argument blocks and launchers of the multi-player path
 // (k_wide.hip) and its orchestration (wide_api.hip).
 #pragma once
+#include <algorithm>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bppo_device.h"
@@ -98,7 +99,19 @@ struct LossArgs {
     // inv = 1 / mb, entropy / value coefficients as the config's f64 values)
     double inv_mb_d, ent_coef_d, value_coef_d;
     int clip_value;
+    // the scalars of a minibatch of mb rows from the config's f64 values: one rule for the
+    // update (wide_minibatch) and the parity hook (bppo_debug_wide_loss)
+    void set_scalars(uint32_t start_, uint32_t mb, double clip_epsilon, double ent_coef_, double value_coef_,
+                     int clip_value_) {
+        start = start_; n = mb;
+        lo = (float)(1.0 - clip_epsilon); hi = (float)(1.0 + clip_epsilon);
+        ceps = (float)clip_epsilon; inv_mb = (float)(1.0 / (double)mb); ent_coef = (float)ent_coef_;
+        value_coef = (float)value_coef_; clip_value = clip_value_;
+        inv_mb_d = 1.0 / (double)mb; ent_coef_d = ent_coef_; value_coef_d = value_coef_;
+    }
 };
+// blocks of 256 rows, capped: beyond 1024 x 256 rows k_wide_loss strides over the grid
+inline int wide_loss_blocks(uint32_t mb) { return std::max(1, std::min(1024, (int)((mb + 255) / 256))); }
 
 // players: Skull's num_players (new_with_players, main.rs:2008-2014); env_seed (device,
 // [N], may be null): env e's seed instead of seed_base + e (evaluation pods)

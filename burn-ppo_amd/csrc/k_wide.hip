@@ -626,3 +626,53 @@ size_t wide_state_bytes(int kind) {
          : kind == BPPO_ENV_CARTPOLE ? sizeof(CartPoleState) : sizeof(LDState);
 }
 }  // namespace bppo
+
+// ------------------------------------------------------------ parity hook ---
+// the masked loss alone (include/bppo.h): host buffers in/out, temporaries of its own, the
+// LossArgs scalars and the block count by wide_minibatch's own rule (bppo_wide.h)
+extern "C" bppo_status bppo_debug_wide_loss(int32_t A, uint32_t n, uint32_t start, uint32_t perm_len,
+                                            uint32_t buf_rows, const uint32_t *perm, const int32_t *act,
+                                            const float *logp, const float *adv, const float *ret, const float *val,
+                                            const uint8_t *mask, const float *logits, const float *values,
+                                            const float *mb_stats, double clip_epsilon, double ent_coef,
+                                            double value_coef, int32_t clip_value, float *dout, float *metrics) {
+    using namespace bppo;
+    constexpr size_t GUARD = 64;
+    if (A != 2 && A != C4_ACT && A != SK_ACT && A != LD_ACT) return BPPO_ERR_ARG;
+    if (n < 1 || buf_rows < 1 || (uint64_t)start + n > perm_len) return BPPO_ERR_ARG;
+    if (!perm || !act || !logp || !adv || !ret || !val || !mask || !logits || !values || !mb_stats || !dout || !metrics)
+        return BPPO_ERR_ARG;
+    for (uint32_t i = 0; i < perm_len; i++)
+        if (perm[i] >= buf_rows) return BPPO_ERR_ARG;
+    for (uint32_t i = 0; i < buf_rows; i++)
+        if (act[i] < 0 || act[i] >= A) return BPPO_ERR_ARG;
+    const int blocks = wide_loss_blocks(n);
+    const size_t n_dout = (size_t)n * (A + 1) + GUARD, n_met = (size_t)WM_COUNT + 1 + GUARD;
+    uint32_t *d_perm = nullptr;
+    int32_t *d_act = nullptr;
+    float *d_logp = nullptr, *d_adv = nullptr, *d_ret = nullptr, *d_val = nullptr, *d_logits = nullptr;
+    float *d_values = nullptr, *d_stats = nullptr, *d_dout = nullptr, *d_met = nullptr;
+    uint8_t *d_mask = nullptr;
+    double *d_part = nullptr;
+    DeviceMem mem;
+    auto up = [&](auto **d, const auto *h, size_t cnt) {
+        return mem.alloc(d, cnt) == hipSuccess &&
+               hipMemcpy(*d, h, cnt * sizeof(**d), hipMemcpyHostToDevice) == hipSuccess;
+    };
+    if (!up(&d_perm, perm, perm_len) || !up(&d_act, act, buf_rows) || !up(&d_logp, logp, buf_rows) ||
+        !up(&d_adv, adv, buf_rows) || !up(&d_ret, ret, buf_rows) || !up(&d_val, val, buf_rows) ||
+        !up(&d_mask, mask, (size_t)buf_rows * A) || !up(&d_logits, logits, (size_t)n * A) ||
+        !up(&d_values, values, n) || !up(&d_stats, mb_stats, 2) || !up(&d_dout, (const float *)dout, n_dout) ||
+        !up(&d_met, (const float *)metrics, n_met) || mem.alloc(&d_part, (size_t)blocks * WM_COUNT) != hipSuccess)
+        return BPPO_ERR_HIP;
+    LossArgs g;
+    g.perm = d_perm; g.act = d_act; g.logp = d_logp; g.adv = d_adv;
+    g.ret = d_ret; g.val = d_val; g.mask = d_mask; g.logits = d_logits; g.values = d_values;
+    g.mb_stats = d_stats; g.dout = d_dout; g.part = d_part;
+    g.set_scalars(start, n, clip_epsilon, ent_coef, value_coef, clip_value);
+    if (wide_loss(A, nullptr, g, blocks, d_met) != hipSuccess) return BPPO_ERR_HIP;
+    if (hipDeviceSynchronize() != hipSuccess) return BPPO_ERR_HIP;
+    if (hipMemcpy(dout, d_dout, n_dout * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return BPPO_ERR_HIP;
+    if (hipMemcpy(metrics, d_met, n_met * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return BPPO_ERR_HIP;
+    return BPPO_OK;
+}

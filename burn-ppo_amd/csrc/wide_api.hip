@@ -269,14 +269,11 @@ bppo_status wide_minibatch(bppo_ctx *c, uint32_t start, uint32_t mb, double ent_
     BPPO_HIP(c, wide_gather(c->stream, c->d_perm, start, mb, c->d_xc, L, c->d_xcg));
     TRY(wide_forward(c, rows, c->d_xcg, L, c->d_logits, c->d_values, split));
     LossArgs g;
-    g.perm = c->d_perm; g.start = start; g.n = mb; g.act = c->d_act; g.logp = c->d_logp; g.adv = c->d_adv;
+    g.perm = c->d_perm; g.act = c->d_act; g.logp = c->d_logp; g.adv = c->d_adv;
     g.ret = c->u_ret; g.val = c->u_val; g.mask = c->d_mask; g.logits = c->d_logits; g.values = c->d_values;
     g.mb_stats = c->d_mb_cur; g.dout = c->d_dout; g.part = c->d_mpart;
-    g.lo = (float)(1.0 - c->cfg.clip_epsilon); g.hi = (float)(1.0 + c->cfg.clip_epsilon);
-    g.ceps = (float)c->cfg.clip_epsilon; g.inv_mb = (float)(1.0 / (double)mb); g.ent_coef = (float)ent_coef;
-    g.value_coef = (float)c->cfg.value_coef; g.clip_value = c->cfg.clip_value;
-    g.inv_mb_d = 1.0 / (double)mb; g.ent_coef_d = ent_coef; g.value_coef_d = c->cfg.value_coef;
-    const int blocks = std::max(1, std::min(1024, (int)((mb + 255) / 256)));
+    g.set_scalars(start, mb, c->cfg.clip_epsilon, ent_coef, c->cfg.value_coef, c->cfg.clip_value);
+    const int blocks = wide_loss_blocks(mb);
     BPPO_HIP(c, wide_loss(A, c->stream, g, blocks, G + n.n_params));
     float *dz = c->d_dz[0], *dz2 = c->d_dz[1];
     auto wgrad = [&](int Kin, int N, const float *X, int ldx, const float *dZ, int ldz, float *dW0, int ldw0,

@@ -772,6 +772,23 @@ bppo_status bppo_debug_slab_reduce(int32_t rows, int32_t width, const float *sla
 bppo_status bppo_debug_adam(int32_t nt, const int32_t *lens, int32_t step, int32_t world, float lr, float max_norm,
                             float eps, int32_t fused, const float *grad, float *params, float *m1, float *m2,
                             const float *gtail, const float *mb_stats, int32_t nm, float *metric_row_out);
+/* bppo_debug_wide_loss: the masked per-row PPO loss of the GEMM path alone (k_wide_loss<A>, A in
+ * {2, 7, 33, 49}, and its metric reduction) with the block count the update launches for n rows.
+ * Minibatch row r < n is buffer row perm[start + r]; perm holds perm_len entries, each below
+ * buf_rows.  Indexed by buffer row: act, logp, adv (raw), ret, val [buf_rows], mask [buf_rows][A]
+ * (0 / 1 bytes).  Indexed by minibatch row: logits [n][A], values [n], as the forward left them.
+ * mb_stats [2] = the minibatch's advantage mean and std (the kernel normalizes with std + 1e-8f).
+ * dout holds n (A + 1) + 64 floats and metrics 14 + 1 + 64; both are uploaded before and read
+ * back after the launches whole, so the caller sees what was written behind the outputs.
+ * dout [n][A + 1] = dL/dlogits | dL/dvalue; metrics [0, 14) = the metric slots in the order of
+ * bppo_minibatch_rows, metrics [14] = the rank-local copy of value_error_max.
+ * BPPO_ERR_ARG before any HIP call: another A, n < 1, buf_rows < 1, start + n > perm_len, a perm
+ * entry >= buf_rows, an action outside [0, A), a NULL pointer. */
+bppo_status bppo_debug_wide_loss(int32_t A, uint32_t n, uint32_t start, uint32_t perm_len, uint32_t buf_rows,
+                                 const uint32_t *perm, const int32_t *act, const float *logp, const float *adv,
+                                 const float *ret, const float *val, const uint8_t *mask, const float *logits,
+                                 const float *values, const float *mb_stats, double clip_epsilon, double ent_coef,
+                                 double value_coef, int32_t clip_value, float *dout, float *metrics);
 /* Parity hook of the evaluation loop's forward (host buffers): the actor logits of n_models
  * models' row groups.  Model k owns rows [gbase[k], gbase[k + 1]) of xc [gbase[n_models]][G + D]
  * ([priv | obs] rows, raw: a model's obs normalizer is applied as the loop applies it) and of

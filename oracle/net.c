@@ -459,28 +459,21 @@ void or_normalize_advantages(const float *adv, size_t n, float *out, float *mean
     if (mx) *mx = hi;
 }
 
-/* ppo.rs:1385-1502 compute_minibatch_loss + autodiff backward (hand-written)
- * and ppo.rs:1507-1592 compute_minibatch_metrics. */
-void or_minibatch_loss_grad(const or_net_desc *d, const float *p, size_t mb, const float *obs,
-                            const float *priv, const int32_t *actions, const float *old_logp,
-                            const float *adv_n, const float *returns, const float *old_values,
-                            const float *masks, const or_ppo_cfg *c, double ent_coef,
-                            float *grads, or_mb_stats *st) {
-    const int A = d->act_dim;
-    float *logits = malloc(sizeof(float) * mb * A);
-    float *values = malloc(sizeof(float) * mb);
-    acts_t acts; memset(&acts, 0, sizeof acts);
-    forward_cached(d, p, obs, priv, mb, logits, values, &acts);
-
+/* The per-row body of or_minibatch_loss_grad on forwarded logits [mb][A] and values [mb]:
+ * ppo.rs:1385-1502 (loss) with its hand-written backward and ppo.rs:1507-1592 (metrics).
+ * dlogits [mb][A], dv [mb]: dL/dlogits and dL/dvalue of the minibatch loss (1 / mb included).
+ * terms [mb][OR_LT_COUNT] (may be NULL): the f32 per-row terms the metrics sum.
+ * decisions [mb][3] (may be NULL): take_rhs (pl1 < pl2: the clipped branch of the policy max;
+ * a tie takes the unclipped one), lo <= ratio <= hi (the clamp passes the gradient, boundaries
+ * included), and the value branch: 0 unclipped (or clip_value off; a tie l1 == l2 goes here),
+ * 1 clipped with -eps <= v - v_old <= eps (gradient passes), 2 clipped and the gradient cut. */
+void or_loss_rows(int A, size_t mb, const float *logits, const float *values, const int32_t *actions,
+                  const float *old_logp, const float *adv_n, const float *returns, const float *old_values,
+                  const float *masks, const or_ppo_cfg *c, double ent_coef, float *dlogits, float *dv,
+                  float *terms, int32_t *decisions) {
     const float lo = (float)(1.0 - c->clip_epsilon_d), hi = (float)(1.0 + c->clip_epsilon_d);
     const float ceps = (float)c->clip_epsilon_d;
     const double inv = 1.0 / (double)mb;
-    float *dlogits = calloc(mb * A, sizeof(float));
-    float *dv = calloc(mb, sizeof(float));
-    double s_pl = 0, s_vl = 0, s_h = 0, s_kl = 0, s_cf = 0, s_v = 0, s_r = 0, s_ve = 0;
-    double s_valid = 0, s_hv = 0, n_choice = 0;
-    float ve_max = -INFINITY;
-    float *verr = malloc(sizeof(float) * mb);
     for (size_t i = 0; i < mb; i++) {
         float x[64], ls[64], pr[64];
         int nvalid = 0;
@@ -502,39 +495,46 @@ void or_minibatch_loss_grad(const or_net_desc *d, const float *p, size_t mb, con
         float pl2 = na * rc;
         int take_rhs = pl1 < pl2;
         float pl = take_rhs ? pl2 : pl1;
-        s_pl += pl;
+        const int in_range = ratio >= lo && ratio <= hi;
         /* value loss */
         float v = values[i], R = returns[i];
         float vl;
         float dvl;  /* d(vl_i)/dv */
+        float dlt = 0.0f;
+        int vbranch = 0;
         if (c->clip_value) {
             float vo = old_values[i];
-            float dlt = v - vo;
+            dlt = v - vo;
             float dc = dlt < -ceps ? -ceps : (dlt > ceps ? ceps : dlt);
             float vc = vo + dc;
             float l1 = (v - R) * (v - R), l2 = (vc - R) * (vc - R);
-            if (l1 < l2) { vl = l2; dvl = (dlt >= -ceps && dlt <= ceps) ? 2.0f * (vc - R) : 0.0f; }
-            else { vl = l1; dvl = 2.0f * (v - R); }
+            if (l1 < l2) {
+                vl = l2;
+                vbranch = (dlt >= -ceps && dlt <= ceps) ? 1 : 2;
+                dvl = vbranch == 1 ? 2.0f * (vc - R) : 0.0f;
+            } else { vl = l1; dvl = 2.0f * (v - R); }
         } else {
             vl = (v - R) * (v - R);
             dvl = 2.0f * (v - R);
         }
-        s_vl += vl;
-        s_h += H;
-        s_kl += (double)((ratio - 1.0f) - log_ratio);
-        s_cf += fabsf(ratio - 1.0f) > ceps ? 1.0 : 0.0;
-        s_v += v; s_r += R;
-        verr[i] = fabsf(v - R);
-        s_ve += verr[i];
-        if (verr[i] > ve_max) ve_max = verr[i];
-        if (masks) {
-            s_valid += nvalid;
-            if (nvalid > 1) { n_choice += 1; s_hv += H / logf((float)nvalid); }
+        if (terms) {
+            float *t = terms + i * OR_LT_COUNT;
+            t[OR_LT_PL] = pl; t[OR_LT_VL] = vl; t[OR_LT_H] = H;
+            t[OR_LT_KL] = (ratio - 1.0f) - log_ratio;
+            t[OR_LT_CF] = fabsf(ratio - 1.0f) > ceps ? 1.0f : 0.0f;
+            t[OR_LT_VE] = fabsf(v - R);
+            t[OR_LT_NVALID] = (float)nvalid;
+            t[OR_LT_HV] = nvalid > 1 ? H / logf((float)nvalid) : 0.0f;
+            t[OR_LT_RATIO] = ratio;
+            t[OR_LT_VDELTA] = dlt;
+        }
+        if (decisions) {
+            decisions[3 * i] = take_rhs; decisions[3 * i + 1] = in_range; decisions[3 * i + 2] = vbranch;
         }
         /* backward: policy term */
         double g_ratio;
         if (!take_rhs) g_ratio = -(double)adv_n[i] * inv;
-        else g_ratio = (ratio >= lo && ratio <= hi) ? -(double)adv_n[i] * inv : 0.0;
+        else g_ratio = in_range ? -(double)adv_n[i] * inv : 0.0;
         double g_lr = g_ratio * (double)ratio;
         for (int a = 0; a < A; a++) {
             double g = g_lr * ((a == actions[i] ? 1.0 : 0.0) - (double)pr[a]);
@@ -543,6 +543,49 @@ void or_minibatch_loss_grad(const or_net_desc *d, const float *p, size_t mb, con
         }
         dv[i] = (float)(c->value_coef * 0.5 * inv * (double)dvl);
     }
+}
+
+/* ppo.rs:1385-1502 compute_minibatch_loss + autodiff backward (hand-written)
+ * and ppo.rs:1507-1592 compute_minibatch_metrics: forward, or_loss_rows, the metric sums over
+ * its per-row terms in row order, then the backward through the net. */
+void or_minibatch_loss_grad(const or_net_desc *d, const float *p, size_t mb, const float *obs,
+                            const float *priv, const int32_t *actions, const float *old_logp,
+                            const float *adv_n, const float *returns, const float *old_values,
+                            const float *masks, const or_ppo_cfg *c, double ent_coef,
+                            float *grads, or_mb_stats *st) {
+    const int A = d->act_dim;
+    float *logits = malloc(sizeof(float) * mb * A);
+    float *values = malloc(sizeof(float) * mb);
+    acts_t acts; memset(&acts, 0, sizeof acts);
+    forward_cached(d, p, obs, priv, mb, logits, values, &acts);
+
+    const double inv = 1.0 / (double)mb;
+    float *dlogits = calloc(mb * A, sizeof(float));
+    float *dv = calloc(mb, sizeof(float));
+    float *terms = malloc(sizeof(float) * mb * OR_LT_COUNT);
+    or_loss_rows(A, mb, logits, values, actions, old_logp, adv_n, returns, old_values, masks, c, ent_coef,
+                 dlogits, dv, terms, NULL);
+    double s_pl = 0, s_vl = 0, s_h = 0, s_kl = 0, s_cf = 0, s_v = 0, s_r = 0, s_ve = 0;
+    double s_valid = 0, s_hv = 0, n_choice = 0;
+    float ve_max = -INFINITY;
+    float *verr = malloc(sizeof(float) * mb);
+    for (size_t i = 0; i < mb; i++) {
+        const float *t = terms + i * OR_LT_COUNT;
+        s_pl += t[OR_LT_PL];
+        s_vl += t[OR_LT_VL];
+        s_h += t[OR_LT_H];
+        s_kl += (double)t[OR_LT_KL];
+        s_cf += t[OR_LT_CF] != 0.0f ? 1.0 : 0.0;
+        s_v += values[i]; s_r += returns[i];
+        verr[i] = t[OR_LT_VE];
+        s_ve += verr[i];
+        if (verr[i] > ve_max) ve_max = verr[i];
+        if (masks) {
+            s_valid += t[OR_LT_NVALID];
+            if (t[OR_LT_NVALID] > 1.0f) { n_choice += 1; s_hv += t[OR_LT_HV]; }
+        }
+    }
+    free(terms);
     float pl_mean = (float)(s_pl * inv);
     float vl_half = (float)(s_vl * inv) * 0.5f;
     float h_mean = (float)(s_h * inv);

@@ -312,6 +312,16 @@ void or_minibatch_loss_grad(const or_net_desc *d, const float *params, size_t mb
                             const float *old_logp, const float *adv_norm, const float *returns,
                             const float *old_values, const float *masks, const or_ppo_cfg *c,
                             double ent_coef, float *grads, or_mb_stats *st);
+/* the row loop of or_minibatch_loss_grad alone, on forwarded logits [mb][A] and values [mb]:
+ * dlogits [mb][A], dv [mb], and per row (either may be NULL) the f32 terms the metrics sum,
+ * terms [mb][OR_LT_COUNT], and decisions [mb][3] = take_rhs, lo <= ratio <= hi, value branch
+ * (0 unclipped, 1 clipped and the gradient passes, 2 clipped and the gradient cut) */
+enum { OR_LT_PL = 0, OR_LT_VL, OR_LT_H, OR_LT_KL, OR_LT_CF, OR_LT_VE, OR_LT_NVALID, OR_LT_HV, OR_LT_RATIO,
+       OR_LT_VDELTA, OR_LT_COUNT };
+void or_loss_rows(int A, size_t mb, const float *logits, const float *values, const int32_t *actions,
+                  const float *old_logp, const float *adv_norm, const float *returns, const float *old_values,
+                  const float *masks, const or_ppo_cfg *c, double ent_coef, float *dlogits, float *dv,
+                  float *terms, int32_t *decisions);
 void or_normalize_advantages(const float *adv, size_t n, float *out, float *mean, float *std,
                              float *mn, float *mx);
 void or_adam_init(or_adam *a, const or_net_desc *d);

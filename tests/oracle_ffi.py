@@ -216,6 +216,8 @@ def lib():
             "or_minibatch_loss_grad": (None, [C.POINTER(NetDesc), f32, C.c_size_t, f32, C.c_void_p,
                                               i32, f32, f32, f32, f32, C.c_void_p, C.POINTER(PpoCfg),
                                               C.c_double, f32, C.POINTER(MbStats)]),
+            "or_loss_rows": (None, [C.c_int, C.c_size_t, f32, f32, i32, f32, f32, f32, f32, C.c_void_p,
+                                    C.POINTER(PpoCfg), C.c_double, f32, f32, f32, i32]),
             "or_trainer_new": (C.c_void_p, [C.POINTER(TrainCfg), f32]),
             "or_trainer_free": (None, [C.c_void_p]),
             "or_trainer_num_params": (C.c_size_t, [C.c_void_p]),
